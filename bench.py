@@ -1,7 +1,13 @@
 """Headline benchmark: end-to-end training step of Howl's audio hot path on synthetic 16 kHz audio (BASELINE.json metric
 "utterances/sec/node (res8, 1s@16kHz, 40-mel)").
 
-    python bench.py --gpus N --steps K --warmup W [--config c3]
+    python bench.py --gpus N --steps K --warmup W [--config c3] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line; everything else it can measure (the roofline
+pass, the CPU baseline, the eval agreement with the oracle, the `like_for_like` and `rccl` legs, the comparison loops of
+``--config eval`` and ``--loop entry``) runs only with ``--full``.  ``--dump-outputs DIR`` writes what the last timed step
+computed -- its loss, its logits and the model state it left (parameters, BatchNorm buffers) -- as DIR/<name>.npy (float32,
+float64 for 64-bit tensors), before any ``--full`` leg runs; the inputs are seeded, so two builds can be compared file by file.
 
 One step = one pass of the hot path over one batch already resident in HBM:
     PCM (B, L) -> fused log-mel frontend (+ZMUV) -> model forward -> loss -> backward
@@ -30,7 +36,7 @@ shuffled ids -> device collate (truncate, Timeshift, Noise, batchify; host draws
 with the oracle of the same loop as ``cpu_baseline``.  ``--prewarm N`` (default 40): untimed steps in front of the W warm-up steps,
 so that the contract's W + K bracket starts at the sustained clock.
 
-Rank 0 prints ONE JSON line; besides the contract fields it carries
+Rank 0 prints ONE JSON line; besides the contract fields it carries ("repeats" always, the rest with ``--full``, else null)
   "roofline":     the time-dominant kernel of the configuration: algorithmic FLOPs (or bytes) per launch / mean launch
                   duration measured with HIP events on the launch stream in a second pass of the same K steps
                   (res8: bwd_pair_kernel = data + weight gradient of a 45->45 layer in one launch, 58 % of the step, vs the
@@ -105,7 +111,37 @@ def parse():
     ap.add_argument("--global-batch", type=int, default=None,
                     help="strong scaling: a FIXED global batch split over the N ranks (configs[2]: 4096); default is weak "
                          "scaling at the configuration's per-GPU batch")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure: roofline pass, CPU baseline, eval agreement, "
+                         "like_for_like (N = 1) and rccl (N > 1) legs, the comparison loops of --config eval / --loop entry")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, logits, model state) as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 22        # elements kept of a larger array: a fixed, seeded sample
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each tensor of ``arrays`` (name -> tensor) as out_dir/<name>.npy: float32, or float64 for 64-bit tensors.  An
+    array of more than DUMP_SAMPLE elements is reduced to the same seeded sample of its flattened entries on every run."""
+    import numpy as np
+    import torch
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        t = t.double() if t.element_size() == 8 else t.float()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            t = t.reshape(-1)[idx]
+        a = t.numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"bench.py --dump-outputs: more than {DUMP_LIMIT_BYTES >> 20} MB at {name}")
+        np.save(out / f"{name}.npy", a)
 
 
 def c5_traffic():
@@ -426,7 +462,8 @@ def bench_entry(args, dev, rank, world):
             trainer.step(pcm_res, labels_res)
         return n * B
 
-    results["resident"] = timed(lambda: resident(args.warmup), lambda: resident(args.steps))
+    if args.full:
+        results["resident"] = timed(lambda: resident(args.warmup), lambda: resident(args.steps))
     writer.close()
     mode = "prefetch" if results["prefetch"][0] <= results["inline"][0] else "inline"
     dt, t_host, seen = results[mode]
@@ -434,19 +471,20 @@ def bench_entry(args, dev, rank, world):
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
-    # host cost of one batch's collate preparation on its own (draws + sort + packed staging buffer)
-    probe = DeviceCollate(bank.audio, bank.lengths_host, bank.labels, L, seed=7)
-    ids = id_batches(1, 3)[0]
-    t0 = time.perf_counter()
-    for _ in range(50):
-        probe.prepare(ids)
-    prep_us = (time.perf_counter() - t0) / 50 * 1e6
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_entry_baseline(L, C, B, args.cpu_baseline_seconds)
+    prep_us = cpu = None
+    if args.full:
+        # host cost of one batch's collate preparation on its own (draws + sort + packed staging buffer)
+        probe = DeviceCollate(bank.audio, bank.lengths_host, bank.labels, L, seed=7)
+        ids = id_batches(1, 3)[0]
+        t0 = time.perf_counter()
+        for _ in range(50):
+            probe.prepare(ids)
+        prep_us = round((time.perf_counter() - t0) / 50 * 1e6, 1)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_entry_baseline(L, C, B, args.cpu_baseline_seconds)
     if rank == 0:
         ms = lambda r: round(r[0] / args.steps * 1e3, 4)
-        res_ms = ms(results["resident"])
+        res_ms = ms(results["resident"]) if args.full else None
         out = {
             "metric": f"utterances/sec/node (res8 entry-point loop: device collate + train-mode frontend + training step, "
                       f"{L / 16000:g}s@16kHz, {MELS}-mel)",
@@ -463,10 +501,10 @@ def bench_entry(args, dev, rank, world):
                        "frontend": "vtlp-train"},
             "loop": {"ms_per_step_prefetch_thread": ms(results["prefetch"]), "ms_per_step_inline_collate": ms(results["inline"]),
                      "ms_per_step_resident_tensors": res_ms,
-                     "entry_over_resident": round(res_ms / (dt / args.steps * 1e3), 4),
+                     "entry_over_resident": round(res_ms / (dt / args.steps * 1e3), 4) if args.full else None,
                      "host_enqueue_ms_per_step": round(t_host / args.steps * 1e3, 4),
-                     "host_enqueue_ms_per_step_resident": round(results["resident"][1] / args.steps * 1e3, 4),
-                     "collate_prepare_us_per_batch": round(prep_us, 1),
+                     "host_enqueue_ms_per_step_resident": round(results["resident"][1] / args.steps * 1e3, 4) if args.full else None,
+                     "collate_prepare_us_per_batch": prep_us,
                      "note": "resident = trainer.step on one batch already in HBM (the default bench line's loop, frontend in train "
                              "mode here); host_enqueue = wall time until the last launch of the K steps was issued -- the entry loop's "
                              "staging ring lets the host run at most eight batches ahead, so there it ends 8 / K before the "
@@ -526,7 +564,10 @@ def bench_eval(args, dev):
         return out
 
     res = {}
-    for name, fn, reps in (("many", many, max(args.steps, 5)), ("batched", batched, max(args.steps, 5)), ("sequential", sequential, 2)):
+    legs = [("many", many, args.steps)]
+    if args.full:
+        legs += [("batched", batched, args.steps), ("sequential", sequential, 2)]
+    for name, fn, reps in legs:
         fn()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -535,20 +576,23 @@ def bench_eval(args, dev):
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / reps
         res[name] = (len(clips) * n_win / dt, dt, out)
-    diff = max(max(float(np.abs(a - b).max()) for a, b in zip(res[k][2], res["sequential"][2])) for k in ("many", "batched"))
-    same = all(np.array_equal(a.argmax(1), b.argmax(1)) for k in ("many", "batched") for a, b in zip(res[k][2], res["sequential"][2]))
+        if name == "many" and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {f"window_probabilities.clip{i}": torch.as_tensor(a) for i, a in enumerate(out)})
+    if args.full:
+        diff = max(max(float(np.abs(a - b).max()) for a, b in zip(res[k][2], res["sequential"][2])) for k in ("many", "batched"))
+        same = all(np.array_equal(a.argmax(1), b.argmax(1)) for k in ("many", "batched") for a, b in zip(res[k][2], res["sequential"][2]))
     print(json.dumps({
         "metric": "windows/sec (res8 streaming evaluation, 500 ms windows / 63 ms stride, 10 s clips)",
-        "value": round(res["many"][0], 1), "unit": "windows/sec", "n_gpus": 1, "steps": max(args.steps, 5), "warmup": 1,
+        "value": round(res["many"][0], 1), "unit": "windows/sec", "n_gpus": 1, "steps": args.steps, "warmup": 1,
         "ms_per_step": round(res["many"][1] * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"FrameInferenceEngine.window_probabilities_many: {len(clips)} clips x 10 s, {n_win} windows each, all "
                                "clips in ONE batch (window gather + frontend + res8 eval forward + softmax + one host copy), as "
                                "training.run.train's evaluation pass scores a dataset", "name": "eval"},
-        "one_batch_per_clip_windows_per_sec": round(res["batched"][0], 1),
-        "sequential_windows_per_sec": round(res["sequential"][0], 1),
-        "speedup_vs_one_window_per_launch": round(res["many"][0] / res["sequential"][0], 1),
-        "agreement": {"argmax_match": same, "max_abs_prob_diff": float(f"{diff:.3e}")},
+        "one_batch_per_clip_windows_per_sec": round(res["batched"][0], 1) if args.full else None,
+        "sequential_windows_per_sec": round(res["sequential"][0], 1) if args.full else None,
+        "speedup_vs_one_window_per_launch": round(res["many"][0] / res["sequential"][0], 1) if args.full else None,
+        "agreement": {"argmax_match": same, "max_abs_prob_diff": float(f"{diff:.3e}")} if args.full else None,
         "note": "sequential = the reference loop's structure (inference.py:223-267: per window a batch-1 forward and a "
                 "device->host copy) on the same kernels"}), flush=True)
 
@@ -556,6 +600,8 @@ def bench_eval(args, dev):
 # ---------------------------------------------------------------------------------------------------------------------
 def main():
     args = parse()
+    if args.dump_outputs and args.loop == "entry" and args.config != "eval":
+        raise SystemExit("bench.py --dump-outputs: not with --loop entry (two timed loops, the faster one is reported)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args.gpus)
         return
@@ -690,13 +736,18 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
     final_loss = loss.item()
+    if args.dump_outputs and rank == 0:
+        # what the caller of the last timed step holds: its loss and logits, and the model state the step left behind
+        # (written before any --full leg steps the model further)
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(-1), "logits": trainer.last_logits,
+                                         **{f"state.{k}": v for k, v in model.state_dict().items()}})
 
     # Like-for-like denominator for a scaling curve: on ONE replica the optimiser step rides in the backward's last fold launch
     # (fused.py: world == 1), on N > 1 replicas it is a launch of its own behind the collective (1 / world scale + AdamW in one
     # kernel, queued behind the all-reduce without a host synchronisation).  At N = 1 the same K steps are therefore timed once
     # more with the optimiser as its own launch (HOWL_NO_FOLD_ADAMW: same bits, tests/test_gpu_lstm.py / test_gpu_res8.py).
     own_launch = None
-    if world == 1 and model_name in ("res8", "seq-lstm") and not args.no_unfused_leg:
+    if args.full and world == 1 and model_name in ("res8", "seq-lstm") and not args.no_unfused_leg:
         os.environ["HOWL_NO_FOLD_ADAMW"] = "1"
         for _ in range(min(args.warmup, 3)):
             step()
@@ -711,7 +762,7 @@ def main():
         del os.environ["HOWL_NO_FOLD_ADAMW"]
 
     rccl = None
-    if world > 1:
+    if args.full and world > 1:
         # the step's one collective, timed on its own (HIP events on the compute stream, which the process group's stream
         # joins on both sides): the flat gradient buffer, sum over ranks
         buf = torch.zeros_like(trainer.fp.grad)
@@ -752,7 +803,8 @@ def main():
 
     roof = None
     lb = hlib.get()
-    if not args.no_roofline:
+    roofline = args.full and not args.no_roofline
+    if roofline:
         # second pass of the same K steps with HIP-event brackets around the dominant kernels.  EVERY rank runs it (the
         # step contains the gradient all-reduce: a rank stepping alone would wait for its peers forever); rank 0 reports.
         if rank == 0:
@@ -762,7 +814,7 @@ def main():
         barrier()
         if rank == 0:
             lb.call("howl_profile_enable", 0)
-    if not args.no_roofline and rank == 0:
+    if roofline and rank == 0:
 
         def read(tag, reset=0):
             tot, cnt, work = ctypes.c_double(0), ctypes.c_int(0), ctypes.c_double(0)
@@ -855,7 +907,7 @@ def main():
         read("logmel", reset=1)
 
     cpu = agree = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         agree = eval_agreement(model_name, model, std, zmuv, pcm, C)
         cpu = cpu_baseline(model_name, L, C, args.cpu_baseline_seconds, bench_batch=B)
 

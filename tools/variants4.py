@@ -75,7 +75,7 @@ def run(names, extra):
     for rep in range(2):
         for name, lib in libs:
             env = dict(os.environ, HOWL_HIP_LIBRARY=str(lib), NUM_MELS="40")
-            r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--no-cpu-baseline", "--steps", "40", "--warmup", "8"] + extra,
+            r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--no-cpu-baseline", "--steps", "40", "--warmup", "8"] + extra,
                                env=env, capture_output=True, text=True, timeout=300)
             try:
                 d = json.loads(r.stdout.strip().splitlines()[-1])
