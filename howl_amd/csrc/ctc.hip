@@ -25,7 +25,7 @@ constexpr int RP = 65;   // LDS row pitch: lanes that walk down a column (lane =
 
 // one wavefront per utterance: ctc_wave (howl_ctc.hip.h)
 __global__ __launch_bounds__(64) void ctc_kernel(const float* __restrict__ logits, long st_t, long st_b, int T, int B, int C,
-                                                 const long long* __restrict__ targets, long tgt_stride,
+                                                 const long long* __restrict__ targets, long tgt_stride, int max_target_length,
                                                  const long long* __restrict__ input_lengths,
                                                  const long long* __restrict__ target_lengths, int blank,
                                                  float* __restrict__ nll_out, float* __restrict__ dlogits, long dst_t,
@@ -33,7 +33,7 @@ __global__ __launch_bounds__(64) void ctc_kernel(const float* __restrict__ logit
     HIP_DYNAMIC_SHARED(float, lds)
     const int b = blockIdx.x;
     ctc_wave<RP>(logits + (size_t)b * st_b, st_t, T, B, C, targets + (size_t)b * tgt_stride, (int)input_lengths[b],
-                 (int)target_lengths[b], blank, nll_out + b, dlogits ? dlogits + (size_t)b * dst_b : nullptr, dst_t, tc,
+                 (int)target_lengths[b], max_target_length, blank, nll_out + b, dlogits ? dlogits + (size_t)b * dst_b : nullptr, dst_t, tc,
                  alpha_ws ? alpha_ws + (size_t)b * T * 64 : nullptr, lds, threadIdx.x);
 }
 
@@ -70,6 +70,8 @@ int howl_ctc_loss(const float* logits, long st_t, long st_b, int T, int B, int C
                   hipStream_t stream) {
     HOWL_REQUIRE(logits && targets && input_lengths && target_lengths && nll, "howl_ctc_loss: null pointer");
     HOWL_REQUIRE(B >= 1 && blank >= 0 && blank < C, "howl_ctc_loss: bad shape (B=%d, blank=%d, C=%d)", B, blank, C);
+    HOWL_REQUIRE(B == 1 || tgt_stride >= max_target_length,
+                 "howl_ctc_loss: target rows of stride %ld overlap (max_target_length %d)", tgt_stride, max_target_length);
     HOWL_REQUIRE(howl_ctc_supported(T, C, max_target_length),
                  "howl_ctc_loss: T=%d C=%d target length %d outside the kernel's range (T <= %d, C <= %d, targets <= %d)", T,
                  C, max_target_length, CTC_MAX_T, CTC_MAX_C, CTC_MAX_L);
@@ -82,7 +84,7 @@ int howl_ctc_loss(const float* logits, long st_t, long st_b, int T, int B, int C
     static thread_local size_t granted[16] = {};
     if (!howl_raise_lds(reinterpret_cast<const void*>(ctc_kernel), lds, granted, "howl_ctc_loss")) return howl_take_pending_error(), HOWL_E_LAUNCH;
     hipLaunchKernelGGL(ctc_kernel, dim3(B), dim3(64), lds, stream, logits, st_t, st_b, T, B, C, targets, tgt_stride,
-                       input_lengths, target_lengths, blank, nll, dlogits, dst_t, dst_b, tc, spills ? workspace : (float*)nullptr);
+                       max_target_length, input_lengths, target_lengths, blank, nll, dlogits, dst_t, dst_b, tc, spills ? workspace : (float*)nullptr);
     if (loss != nullptr)     // NULL: the caller takes the batch mean elsewhere (howl_head_bwd's HowlCtcMean: one launch fewer)
         hipLaunchKernelGGL(ctc_mean_kernel, dim3(1), dim3(256), 0, stream, (const float*)nll, target_lengths, B, loss);
     HOWL_CHECK_LAUNCH("howl_ctc_loss");

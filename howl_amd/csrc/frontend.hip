@@ -97,9 +97,10 @@ __global__ __launch_bounds__(1024) void fb_fragments_kernel(float* __restrict__ 
         if (rm[idx] != 0.0f && !table_has(table, slot_of_bin(k), m >> 2)) uncovered = 1;   // benign race: every writer stores 1
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        reinterpret_cast<int*>(fbp + FBF_OFF)[0] = (table == 0 && !uncovered) ? 1 : 0;
-        reinterpret_cast<int*>(fbp + FBF_OFF)[1] = (table != 0 && !uncovered) ? 1 : 0;
+    // the flag words: [0] / [1] as above, [2 .. 31] reserved (zeros: every word of the packed buffer is written)
+    if (threadIdx.x < HOWL_FB_PACKED_FLOATS - FBF_OFF) {
+        const int v = threadIdx.x == 0 ? (table == 0 && !uncovered) : threadIdx.x == 1 ? (table != 0 && !uncovered) : 0;
+        reinterpret_cast<int*>(fbp + FBF_OFF)[threadIdx.x] = v;
     }
 }
 
@@ -130,9 +131,10 @@ __global__ __launch_bounds__(256) void fb_from_points_kernel(HowlMelPoints pts, 
             if (fb_triangle(pts, M, nyquist, k, m, m0) != 0.0f && !table_has(table, slot_of_bin(k), m >> 2)) uncovered = 1;   // benign race
         }
         __syncthreads();
-        if (threadIdx.x == 0) {
-            reinterpret_cast<int*>(fbp + FBF_OFF)[0] = (table == 0 && !uncovered) ? 1 : 0;
-            reinterpret_cast<int*>(fbp + FBF_OFF)[1] = (table != 0 && !uncovered) ? 1 : 0;
+        // the flag words: [0] / [1] as in fb_fragments_kernel, [2 .. 31] reserved (zeros: every word of the packed buffer is written)
+        if (threadIdx.x < HOWL_FB_PACKED_FLOATS - FBF_OFF) {
+            const int v = threadIdx.x == 0 ? (table == 0 && !uncovered) : threadIdx.x == 1 ? (table != 0 && !uncovered) : 0;
+            reinterpret_cast<int*>(fbp + FBF_OFF)[threadIdx.x] = v;
         }
         return;
     }

@@ -42,6 +42,20 @@ struct CtcLane {
 
 // (every helper below runs in ONE wavefront and synchronises with wave_lds_sync only -- no workgroup barrier -- so that a wave of a
 // larger workgroup can run an utterance's recursion while the other waves do something else: the fused head + CTC kernel of lstm.hip)
+// The contract of howl_ctc_loss / howl_seq_head_ctc (include/howl_hip.h): an utterance whose input length is negative, whose
+// target length is negative or above max_target_length (Lcap), or one of whose labels lies outside [0, C) gets nll = +inf and
+// all-zero gradient rows, and touches nothing of the other utterances.  Such an utterance runs the recursions as an empty one
+// (Tb = L = 0: no label is addressed, no state row is written); the labels are read only up to Lcap.  Wave-uniform result.
+__device__ __forceinline__ bool ctc_out_of_contract(const long long* __restrict__ tgt, int& Tb, int& L, int Lcap, int C, int lane) {
+    bool bad = Tb < 0 || L < 0 || L > Lcap;
+    if (!bad) {
+        const long long lab = lane < L ? tgt[lane] : 0;
+        bad = __ballot(lab < 0 || lab >= C) != 0;
+    }
+    if (bad) Tb = 0, L = 0;
+    return bad;
+}
+
 // phase 1 for the rows [t0, t0 + len) of an utterance: logits -> LDS (flat, independent loads), then lane r turns the
 // window's rows r, r + 64 into log-softmax rows in place (no cross-lane reduction) and clears their posterior rows.
 // A row's bits do not depend on the window it is staged in (a row is recomputed when the backward sweep returns to it).
@@ -131,17 +145,17 @@ __device__ __forceinline__ void ctc_window_grad(const CtcLane& w, int t0, int le
 // workspace) for the beta recursion (carried in a register) and their gradient rows.  2 T_b - (last window) dependent steps.
 template <int RP>
 __device__ __forceinline__ void ctc_wave(const float* __restrict__ zb, long st_t, int T, int B, int C, const long long* __restrict__ tgt,
-                                         int Tb, int L, int blank, float* __restrict__ nll_out, float* __restrict__ db, long dst_t,
-                                         int tc, float* __restrict__ aws, float* __restrict__ lds, int lane) {
+                                         int Tb, int L, int Lcap, int blank, float* __restrict__ nll_out, float* __restrict__ db,
+                                         long dst_t, int tc, float* __restrict__ aws, float* __restrict__ lds, int lane) {
     int* labbuf = reinterpret_cast<int*>(lds + 4 * RP * tc);   // [64]
-    Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+    const bool bad = ctc_out_of_contract(tgt, Tb, L, Lcap, C, lane);
+    Tb = Tb > T ? T : Tb;
     const int S = 2 * L + 1;
     const bool live = lane < S;
     const bool want_grad = db != nullptr;
     // extended labels and the "may skip the blank between two different labels" flags
     int lab = blank;
     if (live && (lane & 1)) lab = (int)tgt[lane >> 1];
-    lab &= 63;
     labbuf[lane] = lab;
     // a row pitch below 64 (the fused head kernel: RP = 17 for <= 8 classes and <= 8 labels) holds the live states only
     const bool wr = RP >= 64 || lane < RP;
@@ -188,7 +202,7 @@ __device__ __forceinline__ void ctc_wave(const float* __restrict__ zb, long st_t
         const float l1 = __shfl(a, S - 1), l2 = S > 1 ? __shfl(a, S - 2) : -INFINITY;
         nll = -lse3(l1, l2, -INFINITY);
     } else {
-        nll = L == 0 ? 0.0f : INFINITY;
+        nll = L == 0 && !bad ? 0.0f : INFINITY;
     }
     if (lane == 0) nll_out[0] = nll;
     if (!want_grad) return;
@@ -235,7 +249,6 @@ __device__ __forceinline__ CtcLane ctc_pair_lane(int role, int T, int C, const l
     const bool live = lane < S;
     int lab = blank;
     if (live && (lane & 1)) lab = (int)tgt[lane >> 1];
-    lab &= 63;
     if (role == 0) labbuf[lane] = lab;
     const int lab_m2 = __shfl(lab, lane >= 2 ? lane - 2 : lane);
     const int lab_p2 = __shfl(lab, lane + 2 < 64 ? lane + 2 : lane);
@@ -252,9 +265,10 @@ __device__ __forceinline__ CtcLane ctc_pair_lane(int role, int T, int C, const l
 // returns nll (role 0; also written to nll_out[0]) -- role 1 returns 0
 template <int RP>
 __device__ __forceinline__ float ctc_pair_recursion(int role, const float* __restrict__ zb, long st_t, int T, int C,
-                                                    const long long* __restrict__ tgt, int Tb, int L, int blank,
+                                                    const long long* __restrict__ tgt, int Tb, int L, int Lcap, int blank,
                                                     float* __restrict__ nll_out, float* __restrict__ lds, int lane) {
-    Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+    const bool bad = ctc_out_of_contract(tgt, Tb, L, Lcap, C, lane);
+    Tb = Tb > T ? T : Tb;
     const CtcLane w = ctc_pair_lane<RP>(role, T, C, tgt, L, blank, true, lds, lane);
     const bool wr = RP >= 64 || lane < RP;
     ctc_stage_rows<RP>(w, zb, st_t, 0, Tb);
@@ -271,7 +285,7 @@ __device__ __forceinline__ float ctc_pair_recursion(int role, const float* __res
             const float l1 = __shfl(a, w.S - 1), l2 = w.S > 1 ? __shfl(a, w.S - 2) : -INFINITY;
             nll = -lse3(l1, l2, -INFINITY);
         } else {
-            nll = L == 0 ? 0.0f : INFINITY;
+            nll = L == 0 && !bad ? 0.0f : INFINITY;
         }
         if (lane == 0) nll_out[0] = nll;
         return nll;
@@ -288,9 +302,10 @@ __device__ __forceinline__ float ctc_pair_recursion(int role, const float* __res
 }
 // role 0's wave, after the workgroup barrier behind both recursions
 template <int RP>
-__device__ __forceinline__ void ctc_pair_grad(int T, int B, int C, const long long* __restrict__ tgt, int Tb, int L, int blank, float nll,
-                                              float* __restrict__ db, long dst_t, float* __restrict__ lds, int lane) {
-    Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+__device__ __forceinline__ void ctc_pair_grad(int T, int B, int C, const long long* __restrict__ tgt, int Tb, int L, int Lcap, int blank,
+                                              float nll, float* __restrict__ db, long dst_t, float* __restrict__ lds, int lane) {
+    ctc_out_of_contract(tgt, Tb, L, Lcap, C, lane);
+    Tb = Tb > T ? T : Tb;
     CtcLane w = ctc_pair_lane<RP>(0, T, C, tgt, L, blank, true, lds, lane);
     const float scale = 1.0f / ((float)B * (float)(L > 0 ? L : 1));
     ctc_window_grad<RP>(w, 0, Tb, blank, nll, scale, db, dst_t);

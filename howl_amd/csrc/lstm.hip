@@ -1067,6 +1067,7 @@ struct SeqHeadArgs {
     float* y2;                 // (B, T, NO) logits
     const long long* targets;
     long tgt_stride;
+    int max_tl;                // max_target_length: a longer target is out of contract (howl_ctc.hip.h ctc_out_of_contract)
     const long long* in_len;
     const long long* tgt_len;
     int blank;
@@ -1203,7 +1204,7 @@ __global__ __launch_bounds__(SH_THREADS) void seq_head_ctc_kernel(SeqHeadArgs a)
         float cnll = 0.0f;
         if (cwave)
             cnll = ctc_pair_recursion<SH_RPC>(crole, lg + (size_t)cu * T * SH_LG, SH_LG, T, NO, a.targets + (size_t)cb * a.tgt_stride,
-                                              (int)a.in_len[cb], (int)a.tgt_len[cb], a.blank, a.nll + cb, cbuf, lane);
+                                              (int)a.in_len[cb], (int)a.tgt_len[cb], a.max_tl, a.blank, a.nll + cb, cbuf, lane);
         HOWL_OPAQUE_S(w1p);
         float wvb[HB_HID / 16][4];
 #pragma unroll
@@ -1215,7 +1216,7 @@ __global__ __launch_bounds__(SH_THREADS) void seq_head_ctc_kernel(SeqHeadArgs a)
         for (int n = 0; n < NO; ++n) w2r[n] = *reinterpret_cast<const float4*>(a.w2 + (long)n * HB_HID + 4 * lane);
         __syncthreads();      // alpha and beta rows of every utterance of the group in LDS
         if (cwave && crole == 0)
-            ctc_pair_grad<SH_RPC>(T, a.B, NO, a.targets + (size_t)cb * a.tgt_stride, (int)a.in_len[cb], (int)a.tgt_len[cb], a.blank, cnll,
+            ctc_pair_grad<SH_RPC>(T, a.B, NO, a.targets + (size_t)cb * a.tgt_stride, (int)a.in_len[cb], (int)a.tgt_len[cb], a.max_tl, a.blank, cnll,
                                   dlg + (size_t)cu * T * SH_LG, SH_LG, cbuf, lane);
         __syncthreads();
         // ---- backward (head_bwd_rows_kernel): dz1 = (y1 > 0) (dlogits W2) -> HBM + tile, dH = dz1 W1, partial sums --------------------
@@ -1680,6 +1681,8 @@ int howl_seq_head_ctc(const HowlHeadParams* p, const float* x, long s_outer, lon
     HOWL_REQUIRE(p && p->w1 && p->b1 && p->w2 && p->b2 && x && targets && input_lengths && target_lengths && y2 && nll && dz1 && dhs &&
                      head_ws, "howl_seq_head_ctc: null pointer");
     HOWL_REQUIRE(blank >= 0 && blank < n_out && max_target_length >= 0, "howl_seq_head_ctc: bad blank / target length");
+    HOWL_REQUIRE(B == 1 || tgt_stride >= max_target_length,
+                 "howl_seq_head_ctc: target rows of stride %ld overlap (max_target_length %d)", tgt_stride, max_target_length);
     SeqHeadGeom g;
     HOWL_REQUIRE(seq_head_geometry(B, T, n_in, n_hid, n_out, max_target_length, &g),
                  "howl_seq_head_ctc: B=%d T=%d (%d -> %d -> %d, targets <= %d) is outside the fused launch's range "
@@ -1693,7 +1696,7 @@ int howl_seq_head_ctc(const HowlHeadParams* p, const float* x, long s_outer, lon
         return HOWL_E_WORKSPACE;
     }
     float* thin = static_cast<float*>(head_ws) + (size_t)HEAD_W1_SPLITS * n_hid * n_in;
-    const SeqHeadArgs a{x, s_outer, s_inner, p->w1, p->b1, p->w2, p->b2, y2, targets, tgt_stride, input_lengths, target_lengths, blank,
+    const SeqHeadArgs a{x, s_outer, s_inner, p->w1, p->b1, p->w2, p->b2, y2, targets, tgt_stride, max_target_length, input_lengths, target_lengths, blank,
                         nll, dz1, dhs, thin, B, T, g.U, g.ngroups};
     HowlProfScope prof("gemm", stream, 4.0 * (double)B * T * n_in * n_hid);
 #define HOWL_SEQ_HEAD(NO)                                                                                                        \

@@ -216,8 +216,8 @@ def _ctc_args(scores, targets, input_lengths, target_lengths, max_target):
         raise ValueError("ctc_loss: a target length exceeds the width of the target matrix")
     dev = scores.device
     targets = targets.to(dev, torch.int64)
-    if targets.shape[1] > 0 and targets.stride(1) != 1:
-        targets = targets.contiguous()
+    if targets.shape[1] > 0 and (targets.stride(1) != 1 or (targets.shape[0] > 1 and targets.stride(0) < max_target)):
+        targets = targets.contiguous()          # rows of max_target labels that do not overlap (an expanded matrix: stride 0)
     return (targets, input_lengths.to(dev, torch.int64).contiguous(), target_lengths.to(dev, torch.int64).contiguous(),
             max_target)
 

@@ -171,7 +171,9 @@ class FusedTrainer:
             # forward recurrence (howl_seq_head_ctc); the model says through `ctc_nll` whether that launch covered the batch
             dev = feat.device
             tg = targets.to(dev, torch.int64)
-            kw["ctc"] = (tg if tg.stride(-1) == 1 else tg.contiguous(), target_lengths.to(dev, torch.int64).contiguous(), int(blank), max_target)
+            if tg.stride(-1) != 1 or (tg.shape[0] > 1 and tg.stride(0) < max_target):
+                tg = tg.contiguous()            # rows of max_target labels that do not overlap (an expanded matrix: stride 0)
+            kw["ctc"] = (tg, target_lengths.to(dev, torch.int64).contiguous(), int(blank), max_target)
             if not ops.on_device(frame_lengths):
                 frame_lengths = frame_lengths.to(torch.int64)
         scores = self.model._launch_forward(feat, frame_lengths, max_frames, **kw)   # (T_len, B, C) view of a (B, T_len, C) buffer

@@ -263,7 +263,12 @@ int howl_xent_fwd_bwd(const float* logits, const long long* labels, int B, int C
  * returns HOWL_E_ARG (the host side raises: the training path has no vendor fallback).  Up to 128 frames an utterance's
  * rows stay in LDS; longer ones (whole clips: AudioSequenceBatchifier, howl/data/transform/batchifier.py:14-34, with the loss
  * over all their frames, train.py:291-296) are walked in windows of 128 frames and, when the gradient is wanted, keep their
- * alpha rows in `workspace`: howl_ctc_workspace_floats(T, B) floats (0 up to 128 frames; workspace may then be NULL). */
+ * alpha rows in `workspace`: howl_ctc_workspace_floats(T, B) floats (0 up to 128 frames; workspace may then be NULL).
+ * Contract per utterance: 0 <= target_lengths[b] <= max_target_length, every label of targets[b][0, target_lengths[b]) in [0, C),
+ * input_lengths[b] >= 0 (an input length above T counts as T).  Rows of targets hold max_target_length labels: tgt_stride >=
+ * max_target_length when B > 1.  An utterance outside the contract gets nll[b] = +inf (so loss = +inf) and all-zero dlogits
+ * rows; only its targets[b][0, max_target_length) are read, and every other utterance's nll and dlogits rows are the bits that
+ * batch gives with that utterance made valid. */
 int howl_ctc_supported(int T, int C, int max_target_length);
 size_t howl_ctc_workspace_floats(int T, int B);
 int howl_ctc_loss(const float* logits, long st_t, long st_b, int T, int B, int C, const long long* targets, long tgt_stride,
@@ -388,7 +393,9 @@ int howl_head_bwd(const HowlHeadParams* p, const float* x, int rows_inner, long 
  * x + b * s_outer + t * s_inner; y2 (B, T, n_out) logits; nll (B); dz1 (B T, n_hid) and dhs (B, T, n_in) as howl_head_bwd leaves
  * them; the per-workgroup partial sums of dW2 / db1 / db2 stay in head_ws (howl_head_workspace_bytes) for howl_seq_lstm_bwd /
  * howl_head_bwd called with y1 = dy2 = NULL, which folds them, takes the first layer's weight gradient and (HowlCtcMean) the
- * batch mean of nll.  Same bits as howl_head_fwd + howl_ctc_loss + howl_head_bwd for y2, nll, dz1, dhs. */
+ * batch mean of nll.  Same bits as howl_head_fwd + howl_ctc_loss + howl_head_bwd for y2, nll, dz1, dhs.  Targets follow
+ * howl_ctc_loss's contract: an utterance outside it gets nll = +inf and all-zero dz1 / dhs rows, and leaves the other utterances'
+ * nll, y2, dz1 and dhs rows as they are with it made valid. */
 int howl_seq_head_ctc_supported(int B, int T, int n_in, int n_hid, int n_out, int max_target_length);
 int howl_seq_head_ctc(const HowlHeadParams* p, const float* x, long s_outer, long s_inner, int B, int T, int n_in, int n_hid, int n_out,
                       const long long* targets, long tgt_stride, int max_target_length, const long long* input_lengths,

@@ -2,8 +2,10 @@
 // TEST INFRASTRUCTURE ONLY (see hip/hip_runtime.h).
 #include "hip/hip_runtime.h"
 
+#include <signal.h>
 #include <sys/mman.h>
 #include <ucontext.h>
+#include <unistd.h>
 #include <vector>
 
 uint3_emu threadIdx, blockIdx;
@@ -47,6 +49,32 @@ void trampoline() {
 }  // namespace
 
 int hipemu_lane() { return cur->lane; }
+
+namespace {
+// (opt-in) a SIGSEGV / SIGBUS inside a launch names the address and the emulated thread, then aborts: the bounds tests'
+// guard pages (tests/guard_mem.py) turn an out-of-bounds access into such a fault at the statement that makes it
+void fault_report(int sig, siginfo_t* si, void*) {
+    char msg[320];
+    const int n = snprintf(msg, sizeof msg,
+                           "hipemu: %s at address %p in block (%u,%u,%u) thread (%u,%u,%u) of grid (%u,%u,%u) x block (%u,%u,%u)%s\n",
+                           sig == SIGBUS ? "SIGBUS" : "SIGSEGV", si->si_addr, blockIdx.x, blockIdx.y, blockIdx.z,
+                           cur ? cur->tid.x : 0u, cur ? cur->tid.y : 0u, cur ? cur->tid.z : 0u, gridDim.x, gridDim.y, gridDim.z,
+                           blockDim.x, blockDim.y, blockDim.z, cur ? "" : " (outside a launch)");
+    if (n > 0) (void)!write(2, msg, (size_t)(n < (int)sizeof msg ? n : (int)sizeof msg - 1));
+    signal(SIGABRT, SIG_DFL);
+    abort();
+}
+}  // namespace
+
+extern "C" void hipemu_enable_fault_report() {
+    struct sigaction sa;
+    memset(&sa, 0, sizeof sa);
+    sa.sa_sigaction = fault_report;
+    sa.sa_flags = SA_SIGINFO | SA_RESETHAND;
+    sigemptyset(&sa.sa_mask);
+    sigaction(SIGSEGV, &sa, nullptr);
+    sigaction(SIGBUS, &sa, nullptr);
+}
 
 void hipemu_syncthreads() { yield(AT_BARRIER); }
 
