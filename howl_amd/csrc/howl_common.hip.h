@@ -1,6 +1,7 @@
 // Shared device/host helpers for the gfx950 kernels behind include/howl_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -75,6 +76,13 @@ struct HowlProfScope {
 struct HowlAdamWCoef {
     float lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale;
 };
+// The coefficients of step `step` (counted from 1): the bias corrections are taken in fp64 and rounded once, here and nowhere else,
+// so that every launch that applies the step (howl_adamw_step, res8's last fold, the LSTM's slab fold) gets the same bits.
+inline HowlAdamWCoef howl_adamw_coef(float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale) {
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    return HowlAdamWCoef{lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale};
+}
 __device__ __forceinline__ void howl_adamw_element(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, size_t i, float g,
                                                    const HowlAdamWCoef& c) {
     // no multiply-add contraction here: the same element must come out bit-identical whichever kernel applies the step (the

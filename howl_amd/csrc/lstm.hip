@@ -1756,10 +1756,9 @@ int howl_seq_lstm_bwd(const HowlHeadParams* hp, int n_hid, int n_out, const floa
     if (lane != nullptr) howl_lane_join(lane, stream);
     if (adamw != nullptr && sums.covers(adamw->g, adamw->n) && getenv("HOWL_NO_FOLD_ADAMW") == nullptr) {
         // every gradient of the model leaves this call through the fold: the optimiser step rides in it
-        const double bc1 = 1.0 - pow((double)adamw->beta1, (double)adamw->step), bc2 = 1.0 - pow((double)adamw->beta2, (double)adamw->step);
         const SlabAdamW opt{adamw->p, adamw->g, adamw->m, adamw->v,
-                            HowlAdamWCoef{adamw->lr, adamw->beta1, adamw->beta2, adamw->eps, adamw->weight_decay, (float)bc1,
-                                          (float)sqrt(bc2), adamw->grad_scale}, 1};
+                            howl_adamw_coef(adamw->lr, adamw->beta1, adamw->beta2, adamw->eps, adamw->weight_decay, adamw->step,
+                                            adamw->grad_scale), 1};
         if (!sums.flush(stream, &opt)) return HOWL_E_ARG;
     } else {
         if (!sums.flush(stream)) return HOWL_E_ARG;

@@ -118,8 +118,6 @@ __device__ __forceinline__ void pack_weights_one(const HowlPtrs6& w, float* __re
     dst[idx] = v;
 }
 
-#define HOWL_PROBE(cfg_, wave_, lane_, slot_) ((void)0)
-
 // ---------------------------------------------------------------------------------------------------------
 // shared pieces of the MFMA kernels
 // ---------------------------------------------------------------------------------------------------------
@@ -671,7 +669,7 @@ struct ConvLoop {
 // barriers per utterance): the register allocator then sees one variant's live values, not the union of all five.
 template <int MODE, int NTW, int TS, int HALO = 0>
 __device__ __forceinline__ void conv_loop(const ConvLoop& c, const ConvEpilogue& epi, const StageCfg& cfg, const int (&pk0)[NS0],
-                                          const int (&pk1)[NS1], int b, float& st0, float& st1, int& pslot,
+                                          const int (&pk1)[NS1], int b, float& st0, float& st1,
                                           const HaloSlot (&hs)[2] = {HaloSlot{-1, 0}, HaloSlot{-1, 0}},
                                           const GridCtx& gx = GridCtx{}) {
     const int P = epi.P, tid = c.tid, lane = c.lane;
@@ -743,9 +741,7 @@ __device__ __forceinline__ void conv_loop(const ConvLoop& c, const ConvEpilogue&
         if constexpr (NTW > 0) k_run<NTW>(k, acc, c.CS, a2);
         HOWL_WINO_BAR();
         HOWL_STAIR(0);
-        HOWL_PROBE(cfg, wave, lane, pslot++);   // phase A done
         __syncthreads();      // channels 24..44 complete; every wave is past its reads of channels 0..23
-        HOWL_PROBE(cfg, wave, lane, pslot++);   // barrier
         // ---- phase B: channels 24..44 feed the matrix pipe, channels 0..23 of the NEXT utterance arrive
         if constexpr (NTW > 0) k_prime<NTW>(k);      // (what the last step of phase A requested ahead predates the barrier)
         if (STAGE && more) {
@@ -792,14 +788,11 @@ __device__ __forceinline__ void conv_loop(const ConvLoop& c, const ConvEpilogue&
             k_tail<NTW>(k, acc, dl);
             HOWL_STAIR(0);
         }
-        HOWL_PROBE(cfg, wave, lane, pslot++);   // phase B done
         // the epilogue runs in front of the barrier: the waves of a SIMD leave the K loop a few hundred cycles apart, and an
         // early one's stores go out under the others' last MFMAs (behind the barrier all twelve epilogues ran with the matrix
         // pipe idle: +1.6 us per forward launch, tools/variants4.py)
         if constexpr (NTW > 0) conv_epilogue<MODE, NTW, TS, HALO>(acc, ev, epi, ubase, c.t0, lane, st0, st1, b, pv);
-        HOWL_PROBE(cfg, wave, lane, pslot++);   // epilogue done
         __syncthreads();      // channels 0..23 of the next utterance complete; every wave is past its reads of 24..44
-        HOWL_PROBE(cfg, wave, lane, pslot++);   // barrier
     }
 }
 
@@ -916,8 +909,6 @@ __device__ __forceinline__ void conv3x3_body(
 
     // channels 0..23 of the first utterance are requested before anything else so that HBM latency overlaps the setup
     int b = bid;
-    int pslot = 0;
-    HOWL_PROBE(cfg, wave, lane, pslot++);   // entry
     SlotVal first[NS0];
     if (b < B) {
 #pragma unroll
@@ -940,7 +931,6 @@ __device__ __forceinline__ void conv3x3_body(
             const int i = tid + j * CONV_THREADS;
             wv[j] = (i < 3 * KSTEPS * 16) ? reinterpret_cast<const float4*>(wp)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        HOWL_PROBE(cfg, wave, lane, pslot++);   // first tile + weights requested
         if (MODE == 0 && folding) {
             // Column sums of the producer's partials while the weight loads are in flight, wave by wave with no LDS
             // scratch and no barrier of their own: wave w owns channels 4w..4w+3 (column groups 0..3: the channels' sums,
@@ -971,15 +961,12 @@ __device__ __forceinline__ void conv3x3_body(
             }
         }
         if (MODE == 1 && cfg.fused) bwd_fold_to_lds(lm, bfold, tid, CONV_THREADS);
-        HOWL_PROBE(cfg, wave, lane, pslot++);   // statistics folded
         zero_lds(tile, TF, tid, CONV_THREADS);
-        HOWL_PROBE(cfg, wave, lane, pslot++);   // tile zeroed
 #pragma unroll
         for (int j = 0; j < 7; ++j) {
             const int i = tid + j * CONV_THREADS;
             if (i < 3 * KSTEPS * 16) reinterpret_cast<float4*>(wl)[i] = wv[j];
         }
-        HOWL_PROBE(cfg, wave, lane, pslot++);   // weights in LDS
     }
     if (MODE == 0 && !folding && tid < CP) {
         lm[tid] = cfg.affine ? -in_stats[tid] * in_stats[CP + tid] : 0.0f;     // slot_write: xhat = |s| * rstd + this
@@ -996,7 +983,6 @@ __device__ __forceinline__ void conv3x3_body(
     const ConvEpilogue epi{res, out, xs, xshift, xrstd, cout, P, cvalid, MODE == 1 && xs != nullptr && xs_stats == nullptr,
                            pool, 4 * slices, t0};
     __syncthreads();  // weights, zero fill and the per-channel constants visible before the first stage
-    HOWL_PROBE(cfg, wave, lane, pslot++);   // setup barrier passed
     if (b < B) {
 #pragma unroll
         for (int j = 0; j < NS0; ++j)
@@ -1006,19 +992,17 @@ __device__ __forceinline__ void conv3x3_body(
         if constexpr (HALO == 2) grid_write<MODE>(firstg, cfg, gx, 0, b, H, tile, lm);
     }
     __syncthreads();  // channels 0..23 of the first utterance in place
-    HOWL_PROBE(cfg, wave, lane, pslot++);   // first half tile staged
 
     const ConvLoop cl{(const lds_f32*)tile, (const lds_f32*)wl + nt * KSTEPS * 64, tile, lm, B, CS, t0, lane, tid, nblk};
     switch (ntw) {
-        case 5: conv_loop<MODE, 5, ts, HALO>(cl, epi, cfg, pk0, pk1, b, st0, st1, pslot, hs, gx); break;
-        case 4: conv_loop<MODE, 4, ts, HALO>(cl, epi, cfg, pk0, pk1, b, st0, st1, pslot, hs, gx); break;
-        case 3: conv_loop<MODE, 3, ts, HALO>(cl, epi, cfg, pk0, pk1, b, st0, st1, pslot, hs, gx); break;
-        case 2: conv_loop<MODE, 2, ts, HALO>(cl, epi, cfg, pk0, pk1, b, st0, st1, pslot, hs, gx); break;
-        case 1: conv_loop<MODE, 1, ts, HALO>(cl, epi, cfg, pk0, pk1, b, st0, st1, pslot, hs, gx); break;
-        default: conv_loop<MODE, 0, ts, HALO>(cl, epi, cfg, pk0, pk1, b, st0, st1, pslot, hs, gx); break;
+        case 5: conv_loop<MODE, 5, ts, HALO>(cl, epi, cfg, pk0, pk1, b, st0, st1, hs, gx); break;
+        case 4: conv_loop<MODE, 4, ts, HALO>(cl, epi, cfg, pk0, pk1, b, st0, st1, hs, gx); break;
+        case 3: conv_loop<MODE, 3, ts, HALO>(cl, epi, cfg, pk0, pk1, b, st0, st1, hs, gx); break;
+        case 2: conv_loop<MODE, 2, ts, HALO>(cl, epi, cfg, pk0, pk1, b, st0, st1, hs, gx); break;
+        case 1: conv_loop<MODE, 1, ts, HALO>(cl, epi, cfg, pk0, pk1, b, st0, st1, hs, gx); break;
+        default: conv_loop<MODE, 0, ts, HALO>(cl, epi, cfg, pk0, pk1, b, st0, st1, hs, gx); break;
     }
 
-    HOWL_PROBE(cfg, wave, lane, pslot++);   // all utterances done
     if (part != nullptr) {
         // lanes l, l^16, l^32, l^48 hold the same cout: fold them, then fold the 4 position groups via LDS
         st0 += __shfl_xor(st0, 16);
@@ -1395,7 +1379,7 @@ __device__ __forceinline__ int wgrad_boff(int q, int n, int g, int CSX) {
 
 template <int NB, bool EX, int GWS, int HALO = 0>
 __device__ __forceinline__ void wgrad_loop(const WgradArgs& a, const int (&zt)[WNT], const int (&xt)[WNT], const int (&ct)[WNT],
-                                           const int (&zb)[WNB], const int (&xb)[WNB], const int (&cb)[WNB], int b, int& pslot,
+                                           const int (&zb)[WNB], const int (&xb)[WNB], const int (&cb)[WNB], int b,
                                            const WHalo (&wh)[2] = {WHalo{-1, 0, 0, 0}, WHalo{-1, 0, 0, 0}},
                                            const WGridCtx& gx = WGridCtx{}) {
     const int lane = a.lane, wave = a.wave;
@@ -1480,9 +1464,7 @@ __device__ __forceinline__ void wgrad_loop(const WgradArgs& a, const int (&zt)[W
         if (R1 > 2) wgrad_k_run<NB, EX>(c, acc, acce, az, bx, aze, bxe, R1 - 2);
         HOWL_STAIR(0);
         HOWL_W_WRITE(0, 4, zb, xb, cb, zb_, gx.pzb, gx.pxb);
-        HOWL_PROBE(a.st.z, wave, lane, pslot++);   // phase 1 done
         __syncthreads();      // bottom rows complete; every wave is past its reads of the top rows
-        HOWL_PROBE(a.st.z, wave, lane, pslot++);   // barrier
         // ---- phase 2: rounds R1 .. R-1 on the bottom rows (x: region 2, two tile rows further down); the top rows of the
         // next utterance arrive.  The operands requested ahead by the last k-step of phase 1 predate the barrier: re-read.
 #pragma unroll
@@ -1523,9 +1505,7 @@ __device__ __forceinline__ void wgrad_loop(const WgradArgs& a, const int (&zt)[W
         HOWL_STAIR(0);
 #undef HOWL_W_LOAD
 #undef HOWL_W_WRITE
-        HOWL_PROBE(a.st.z, wave, lane, pslot++);   // phase 2 done
         __syncthreads();      // top rows of the next utterance complete; every wave is past its reads of the bottom rows
-        HOWL_PROBE(a.st.z, wave, lane, pslot++);   // barrier
     }
     // D[row = cout = 16mt + 4*(lane>>4) + r][col = n = lane&15] of N tile q -> partial row [48][WNCOL], column 16 q + n
     float* dst = a.part + (size_t)a.bid * CP * WNCOL;
@@ -1561,8 +1541,6 @@ __device__ __forceinline__ void wgrad_body(
     const int R = wgrad_rounds(H), R1 = wgrad_r1(H);
     st.xaffine = in_stats != nullptr;
     st.z.ds = nullptr;                      // ds_i is written by the data gradient's staging
-    int pslot = 0;
-    HOWL_PROBE(st.z, wave, lane, pslot++);   // entry
 
     // row regions: phase 1 reads z rows < 4 R1 and x halo rows <= 4 R1 + 1 (data rows <= 4 R1); phase 2 the z rows >= 4 R1 and
     // x halo rows >= 4 R1 (data rows >= 4 R1 - 1), kept two tile rows further down
@@ -1626,7 +1604,6 @@ __device__ __forceinline__ void wgrad_body(
         if constexpr (HALO == 2) wrow_write(firstr, st.xaffine, gx, b, H, false, tx, lm);
     }
     __syncthreads();
-    HOWL_PROBE(st.z, wave, lane, pslot++);   // prologue done
     // instantiated per tile count (waves 0..2 carry a third N tile): no branches inside the K loop, and the register
     // allocator sees one variant's live values (waves of a workgroup run different instances with the same barriers)
     // small batches: two workgroups share an utterance group's 27 N tiles (each stages both maps; wave gw of the 24 owns tiles
@@ -1648,9 +1625,9 @@ __device__ __forceinline__ void wgrad_body(
         }
         const WgradArgs a{st, part, tz, tx, lm, B, P, CSZ, CSX, R, R1, tid, lane, wave, bid, nblk, gw, qe, mte};
         if (ex)
-            wgrad_loop<2, true, GWS, HALO>(a, zt, xt, ct, zb, xb, cb, b, pslot, wh, gx);
+            wgrad_loop<2, true, GWS, HALO>(a, zt, xt, ct, zb, xb, cb, b, wh, gx);
         else
-            wgrad_loop<2, false, GWS, HALO>(a, zt, xt, ct, zb, xb, cb, b, pslot, wh, gx);
+            wgrad_loop<2, false, GWS, HALO>(a, zt, xt, ct, zb, xb, cb, b, wh, gx);
     } else {
         // small batches: tile gw for each of the 24 waves of the two workgroups; the six chains of tiles 24 / 25 (three cout tiles
         // each) go one each to waves 0, 1, 2 of either workgroup -- three different SIMDs (round 6: as whole tiles on waves 0 / 1 of
@@ -1660,11 +1637,10 @@ __device__ __forceinline__ void wgrad_body(
         const bool ex = wave < 3;
         const WgradArgs a{st, part, tz, tx, lm, B, P, CSZ, CSX, R, R1, tid, lane, wave, bid, nblk, gw, 24 + slice, ex ? wave : 0};
         if (ex)
-            wgrad_loop<1, true, GWS, HALO>(a, zt, xt, ct, zb, xb, cb, b, pslot, wh, gx);
+            wgrad_loop<1, true, GWS, HALO>(a, zt, xt, ct, zb, xb, cb, b, wh, gx);
         else
-            wgrad_loop<1, false, GWS, HALO>(a, zt, xt, ct, zb, xb, cb, b, pslot, wh, gx);
+            wgrad_loop<1, false, GWS, HALO>(a, zt, xt, ct, zb, xb, cb, b, wh, gx);
     }
-    HOWL_PROBE(st.z, wave, lane, pslot++);   // partials written
 }
 
 template <int SLICES, int HALO = 0>
@@ -2495,16 +2471,21 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
         howl_adamw_element(p, m, v, i, g[i], c);
 }
 
+}  // namespace (device code)
+
+// ===============================================================================================================================
+// host side: the launch plan, the launchers, the entry points of include/howl_hip.h
+// ===============================================================================================================================
+namespace {
+
 size_t conv0_tile_floats(int T, int M) { return (size_t)(T + 2) * (M + 4) + 3 * (M + 4) + 16; }   // tile + slack (conv0_fwd_mfma_kernel)
-size_t conv_lds_bytes(int H, bool own_rows = false) {
+size_t conv_lds_bytes(int H, bool own_rows) {
     return (size_t)(3 * KSTEPS * 64 + tile_floats(H, own_rows) + 4 * CP + 12 * 2 * 16) * sizeof(float);
 }
-StageCfg with_probe(StageCfg c) { return c; }
-
 size_t wgrad_lds_bytes(int H) { return (size_t)(tile_floats_z(H) + tile_floats_x(H) + 6 * CP) * sizeof(float); }
 
 struct Ws {
-    float* wp_fwd;   // [6][3][108][64]
+    float* wp_fwd;   // [6][3][KSTEPS][64]
     float* wp_bwd;
     float* part;     // statistics partials, transposed [2][48][part_stride(G)] (fold_part_column)
     float* part2;    // second set: a forward layer writes one while the next layer's prologue may still read the other
@@ -2524,7 +2505,7 @@ struct Ws {
 
 // `fwd_eval_bytes`: what an eval-mode forward touches (packed weights, statistics, pooled sums: everything in front of the
 // backward's activation-sized buffers)
-size_t ws_layout(Ws* w, char* base, int B, int H, int G, size_t* fwd_eval_bytes = nullptr) {
+size_t ws_layout(Ws* w, char* base, int B, int H, int G, int cus, size_t* fwd_eval_bytes) {
     size_t off = 0;
     auto take = [&](size_t floats) {
         float* p = base ? reinterpret_cast<float*>(base + off) : nullptr;
@@ -2532,96 +2513,205 @@ size_t ws_layout(Ws* w, char* base, int B, int H, int G, size_t* fwd_eval_bytes 
         return p;
     };
     const size_t act = (size_t)B * NMAP * H * PW;
-    Ws t;
-    t.wp_fwd = take((size_t)6 * 3 * KSTEPS * 64);
-    t.wp_bwd = take((size_t)6 * 3 * KSTEPS * 64);
-    const int max_parts = G > howl_num_cus() ? G : howl_num_cus();     // one row per workgroup; slicing never exceeds the CU count
-    t.part = take((size_t)part_stride(max_parts) * 2 * CP);
-    t.part2 = take((size_t)part_stride(max_parts) * 2 * CP);
-    t.stats = take((size_t)6 * 2 * CP);
-    t.m12 = take(2 * CP);
-    t.dpool = take((size_t)B * CP);
-    t.pool = take((size_t)B * 16 * CP);
-    if (fwd_eval_bytes) *fwd_eval_bytes = off;
-    t.bufa = take(act);
-    t.bufb = take(act);
-    t.dz = take(act);
-    t.dz2 = take(act);
-    t.dsa = take(act);
-    t.dsb = take(act);
-    t.wpart = take((size_t)6 * G * CP * WNCOL);
-    t.c0part = take((size_t)max_parts * NMAP * 9);     // one row per workgroup of conv0's weight gradient (<= CUs with slicing)
-    if (w) *w = t;
+    w->wp_fwd = take((size_t)6 * 3 * KSTEPS * 64);
+    w->wp_bwd = take((size_t)6 * 3 * KSTEPS * 64);
+    const int max_parts = G > cus ? G : cus;     // one row per workgroup; slicing never exceeds the CU count
+    w->part = take((size_t)part_stride(max_parts) * 2 * CP);
+    w->part2 = take((size_t)part_stride(max_parts) * 2 * CP);
+    w->stats = take((size_t)6 * 2 * CP);
+    w->m12 = take(2 * CP);
+    w->dpool = take((size_t)B * CP);
+    w->pool = take((size_t)B * 16 * CP);
+    *fwd_eval_bytes = off;
+    w->bufa = take(act);
+    w->bufb = take(act);
+    w->dz = take(act);
+    w->dz2 = take(act);
+    w->dsa = take(act);
+    w->dsb = take(act);
+    w->wpart = take((size_t)6 * G * CP * WNCOL);
+    w->c0part = take((size_t)max_parts * NMAP * 9);     // one row per workgroup of conv0's weight gradient (<= CUs with slicing)
     return off;
 }
 
-// Backward pass: per layer  bn_relu_bwd -> [dgrad || wgrad in one launch, half the CUs each] -> bn_bwd_finalize, all on the
-// caller's stream; every layer's weight-gradient partials stay in the workspace and ONE launch reduces them all at the
-// end (nothing but AdamW waits for them).  HOWL_RES8_BWD_PAIR=0 launches the two halves one after the other with the
-// same grids (bit-identical results; the reference point of the tests).
-int conv_grid(int B) {
-    int g = howl_num_cus();
-    return B < g ? B : g;
-}
 // Mel bins -> strips of 10 pooled columns (see HaloSlot): 40 -> 1, 80 -> 2 (the reference's stock NUM_MELS, settings.py:32)
 int mel_strips(int M) { return M == 40 ? 1 : (M == 80 ? 2 : 0); }
 // a workgroup's utterances b, b + nblk, ... must keep their strip parity on wide maps: an even stride (B = 2 x utterances >= 2)
-// How (B, T, M) runs as blocks of (45, Hs, 10): ns column strips (mel_strips) x nr row strips of Hs <= 27 pooled rows, the last row
-// strip with hv_last valid rows (StripGeom); halo = 0: plain utterances, 1: column strips only (HaloSlot), 2: row strips
-struct Strips {
-    int ns, nr, Hs, hv_last, Bv, halo;
-    StripGeom sg;
-};
-Strips strips_for(int B, int T, int M) {
-    Strips st;
-    const int H = T / 3;
-    st.ns = mel_strips(M) > 0 ? mel_strips(M) : 1;
-    st.nr = H <= MAX_H ? 1 : (H + MAX_H - 1) / MAX_H;
-    st.Hs = (H + st.nr - 1) / st.nr;
-    st.hv_last = H - (st.nr - 1) * st.Hs;
-    st.Bv = B * st.nr * st.ns;
-    st.halo = st.nr > 1 ? 2 : (st.ns > 1 ? 1 : 0);
-    st.sg = StripGeom{st.nr, st.ns, st.hv_last};
-    return st;
-}
 int even_grid(int g, int strips) { return strips > 1 ? ((g & ~1) > 2 ? (g & ~1) : 2) : g; }
+int launch_blocks(int nblk, int per_group) { return 8 * per_group * ((nblk + 7) / 8); }
 // Small batches (the reference's presets train at 16, its engines run at batch 1): how many workgroups share one utterance.
 // Forward / data gradient split the position tiles (4 or 2 ways: every position group of a workgroup keeps at least one
 // tile), the weight gradient its 27 N tiles (2 ways).
-int launch_blocks(int nblk, int per_group) { return 8 * per_group * ((nblk + 7) / 8); }
-bool slicing_enabled() {     // HOWL_RES8_SLICES=0: one workgroup per utterance whatever the batch (the reference point of the tests)
-    const char* e = getenv("HOWL_RES8_SLICES");
-    return !(e != nullptr && e[0] == '0');
-}
 int conv_slices(int nblk, int H, int budget) {
     const int ntiles = (H * PW + 15) / 16;
-    if (!slicing_enabled()) return 1;
     for (int sl = 4; sl > 1; sl >>= 1)
         if (nblk * sl <= budget && 4 * sl <= ntiles) return sl;
     return 1;
 }
-// conv0 (forward and weight gradient): up to eight workgroups share an utterance's pooled rows / cells while B * slices <= CUs
-int conv0_slices(int B) {
-    if (!slicing_enabled()) return 1;
-    int sl = howl_num_cus() / (B > 0 ? B : 1);
-    return sl < 1 ? 1 : (sl > 8 ? 8 : sl);
-}
-void pair_slices(int nblk, int H, int* sd, int* sw) {
-    const int cus = howl_num_cus(), ntiles = (H * PW + 15) / 16;
-    const int opts[4][2] = {{4, 2}, {2, 2}, {2, 1}, {1, 1}};
+void pair_slices(int nblk, int H, int cus, int* sd, int* sw) {
+    const int ntiles = (H * PW + 15) / 16;
+    const int opts[3][2] = {{4, 2}, {2, 2}, {2, 1}};
     *sd = *sw = 1;
-    if (!slicing_enabled()) return;
     for (const auto& o : opts)
         if (nblk * (o[0] + o[1]) <= cus && 4 * o[0] <= ntiles) {
             *sd = o[0];
             *sw = o[1];
             return;
         }
-    *sd = *sw = 1;
+}
+// conv0 (forward and weight gradient): up to eight workgroups share an utterance's pooled rows / cells while B * slices <= CUs
+int conv0_slices(int B, int cus) {
+    const int sl = cus / (B > 0 ? B : 1);
+    return sl < 1 ? 1 : (sl > 8 ? 8 : sl);
+}
+bool env_off(const char* name) {      // "NAME=0" switches a default-on path off
+    const char* e = getenv(name);
+    return e != nullptr && e[0] == '0';
 }
 
-// launchers: one instantiation per slicing factor (dynamic LDS limit raised on the instance that is launched)
+// howl_res8_fwd_long: the kernels keep one utterance's whole (45, H, 10) map in LDS, H <= 27 pooled rows (83 frames).  A longer
+// clip is cut into windows of 27 pooled rows that overlap by 14: the six 3x3 convolutions (and conv0's own frame) spread a
+// window's zero padding 7 rows inwards, so a window's rows [7, 20) -- [0, 20) for the first, [7, 27) for the last -- are exactly
+// what the unbounded convolution stack computes, and those ranges tile the clip.  Inference statistics are per channel constants,
+// so nothing couples the windows except the final spatial mean.  (Training on such windows would need BatchNorm batch
+// statistics over the de-duplicated rows: not offered; the reference's training windows are <= 1 s.)
+constexpr int WIN_H = MAX_H, WIN_MARGIN = 7, WIN_STEP = WIN_H - 2 * WIN_MARGIN;   // 27, 7, 13
+int long_windows(int H) { return H <= WIN_H ? 1 : (H - WIN_H + WIN_STEP - 1) / WIN_STEP + 1; }
+
+// How one problem (B, T, M) runs: everything the host derives from the shape, the CU count and the environment switches.  Built
+// per call (the tests flip the switches inside one process) by res8_plan / res8_long_plan and by nobody else: the size queries
+// and the launches read the same fields.
+struct Res8Plan {
+    // blocks of (45, Hs, 10): ns column strips (mel_strips) x nr row strips of Hs <= 27 pooled rows, the last row strip with
+    // hv_last valid rows (StripGeom); halo = 0: plain utterances, 1: column strips only (HaloSlot), 2: row strips
+    int B, T, M, ns, nr, Hs, hv_last, Bv, halo;
+    StripGeom sg;
+    int P, Pt;      // positions of one block; of one utterance's whole map
+    // HOWL_RES8_SLICES=0: one workgroup per utterance whatever the batch; HOWL_RES8_BWD_PAIR=0: data and weight gradient as two
+    // launches with the same grids; HOWL_RES8_BWD_FUSED=0: the elementwise BatchNorm / ReLU backward as its own launch per
+    // layer (strips: the fused staging only) -- each bit-identical to the default, the reference points of the tests
+    bool slicing, merged, fused;
+    // forward 3x3: G workgroup groups x SL position slices
+    int G, SL;
+    size_t lds_conv;
+    // conv0 forward over Bw inputs of Tw frames (an utterance; for row strips its nr windows of 3 Hs frames with the clip's real
+    // frames on both sides: c0_exact), S0 workgroups each: 103 VGPRs and 15 KB of LDS, two workgroups per CU overlap one's tile
+    // load / stores with the other's MFMAs
+    int Bw, Tw, S0, G0, c0_nwin, c0_step, c0_last;
+    bool c0_exact;
+    size_t lds_conv0;
+    // backward 3x3: data and weight gradient side by side on half the CUs each: Gh groups x (SD position + SW N-tile slices)
+    int Gh, SD, SW, ew_grid;      // ew_grid: bn_relu_bwd_kernel, one 16-byte quad per thread and trip
+    // the fold of a layer's weight-gradient partials rides in the NEXT pair launch when that launch has enough data-gradient
+    // workgroups to spread the 9,984 column pairs thin (a single utterance's four workgroups would walk 26 trips of two barriers
+    // each: +60 us at batch 1); small batches keep the one reduction launch at the end
+    bool fold_in_pair;
+    size_t wpart_stride, lds_wgrad, lds_pair;
+    // conv0's weight gradient: G0w workgroups (one partial row each), S0w per block.  Its work items are the Bv blocks, the
+    // forward's the Bw inputs (one item writes both column strips of its rows): S0w and S0 differ at 80 mel bins, as intended
+    int S0w, G0w;
+    size_t lds_conv0w;
+    // sizes, and the workspace laid out at the caller's pointer (null for a size query)
+    size_t saved_floats, train_bytes, eval_bytes;
+    size_t long_map_bytes, long_bytes;      // res8_long_plan: one of the three rotating maps; the whole workspace
+    Ws ws;
+};
+
+// everything behind the block geometry and conv0's windows, which the two builders set
+void plan_launches(Res8Plan& p, bool slice_conv0, char* ws_base) {
+    const int cus = howl_num_cus(), H = p.Hs;
+    p.P = H * PW;
+    p.Pt = (p.T / 3) * PW * p.ns;
+    p.saved_floats = (size_t)p.Bv * NMAP * p.P;
+    p.slicing = !env_off("HOWL_RES8_SLICES");
+    p.merged = !env_off("HOWL_RES8_BWD_PAIR");
+    p.fused = p.halo != 0 || !env_off("HOWL_RES8_BWD_FUSED");
+
+    p.G = even_grid(p.Bv < cus ? p.Bv : cus, p.ns);
+    p.SL = p.halo == 0 && p.slicing ? conv_slices(p.G, H, cus) : 1;
+    p.lds_conv = conv_lds_bytes(H, p.halo == 2);
+    p.S0 = slice_conv0 && p.slicing ? conv0_slices(p.Bw, cus) : 1;
+    p.G0 = p.Bw * p.S0 < 2 * cus ? p.Bw * p.S0 : 2 * cus;
+    p.lds_conv0 = conv0_tile_floats(p.Tw, p.M) * sizeof(float);
+
+    const int half = cus / 2 > 0 ? cus / 2 : 1;
+    p.Gh = even_grid(p.Bv < half ? p.Bv : half, p.ns);
+    p.SD = p.SW = 1;
+    if (p.halo == 0 && p.slicing) pair_slices(p.Gh, H, cus, &p.SD, &p.SW);
+    p.fold_in_pair = p.Gh * p.SD >= 64;
+    p.wpart_stride = (size_t)p.Gh * CP * WNCOL;
+    p.lds_wgrad = wgrad_lds_bytes(H);
+    p.lds_pair = p.lds_conv > p.lds_wgrad ? p.lds_conv : p.lds_wgrad;
+    const size_t quads = (p.saved_floats / 4 + BRB_THREADS - 1) / BRB_THREADS;
+    p.ew_grid = quads < 1 ? 1 : (quads > (size_t)(2 * cus) ? 2 * cus : (int)quads);
+    p.S0w = p.slicing ? conv0_slices(p.Bv, cus) : 1;
+    p.G0w = p.Bv * p.S0w < cus ? p.Bv * p.S0w : cus;
+    p.lds_conv0w = ((size_t)(p.Tw + 2) * (p.M + 4) + 16) * sizeof(float);
+
+    p.train_bytes = ws_layout(&p.ws, ws_base, p.Bv, H, p.G, cus, &p.eval_bytes);
+}
+
+// howl_res8_fwd / _bwd and their size queries
+Res8Plan res8_plan(int B, int T, int M, void* ws = nullptr) {
+    Res8Plan p{};
+    const int H = T / 3;
+    p.B = B, p.T = T, p.M = M;
+    p.ns = mel_strips(M) > 0 ? mel_strips(M) : 1;
+    p.nr = H <= MAX_H ? 1 : (H + MAX_H - 1) / MAX_H;
+    p.Hs = (H + p.nr - 1) / p.nr;
+    p.hv_last = H - (p.nr - 1) * p.Hs;
+    p.Bv = B * p.nr * p.ns;
+    p.halo = p.nr > 1 ? 2 : (p.ns > 1 ? 1 : 0);
+    p.sg = StripGeom{p.nr, p.ns, p.hv_last};
+    p.c0_exact = p.halo == 2;
+    p.Bw = B * p.nr;
+    p.Tw = p.c0_exact ? 3 * p.Hs : T;
+    p.c0_nwin = p.c0_exact ? p.nr : 1;
+    p.c0_step = p.c0_exact ? 3 * p.Hs : 0;
+    p.c0_last = p.c0_exact ? T : 0;
+    plan_launches(p, true, static_cast<char*>(ws));
+    return p;
+}
+
+// howl_res8_fwd_long and its size query: the windows of all clips as a virtual batch of plain (halo 0) or column-strip (halo 1)
+// blocks of WIN_H rows; in front of the regular workspace of that batch lie three rotating activation maps and the eval statistics
+Res8Plan res8_long_plan(int B, int T, int M, void* ws = nullptr) {
+    Res8Plan p{};
+    const int H = T / 3, nw = long_windows(H);
+    p.B = B, p.T = T, p.M = M;
+    p.ns = mel_strips(M) > 0 ? mel_strips(M) : 1;
+    p.nr = 1, p.Hs = p.hv_last = WIN_H;
+    p.Bv = B * nw * p.ns;
+    p.halo = p.ns > 1 ? 1 : 0;
+    p.sg = StripGeom{1, 1, 0};
+    // T % 3 trailing frames take no part in the pooling but are conv0's neighbours of the clip's last frame: every window
+    // reads them too (inner windows simply see real samples there instead of padding, inside their discarded margin)
+    p.Bw = B * nw;
+    p.Tw = 3 * WIN_H + T % 3;
+    p.c0_nwin = nw, p.c0_step = 3 * WIN_STEP, p.c0_last = 3 * (H - WIN_H);
+    static_assert((6 * 2 * CP * sizeof(float)) % 256 == 0, "statistics block keeps the 256-byte alignment");
+    p.long_map_bytes = ((size_t)p.Bv * NMAP * WIN_H * PW * sizeof(float) + 255) / 256 * 256;
+    const size_t front = 3 * p.long_map_bytes + 6 * 2 * CP * sizeof(float) + 256;
+    plan_launches(p, false, ws ? static_cast<char*>(ws) + front : nullptr);      // (conv0: one workgroup per window)
+    p.long_bytes = front + p.train_bytes;
+    return p;
+}
+
+int check_workspace(const char* who, size_t have, size_t need) {
+    if (have >= need) return HOWL_OK;
+    howl_set_error("%s: workspace %zu < %zu bytes", who, have, need);
+    return HOWL_E_WORKSPACE;
+}
+template <class T>
+HowlPtrs6 ptrs6(T* const (&a)[6]) {
+    HowlPtrs6 r;
+    for (int i = 0; i < 6; ++i) r.p[i] = const_cast<float*>(a[i]);
+    return r;
+}
 StageCfg plain_tile(const float* t) { return StageCfg{t, nullptr, nullptr, nullptr, nullptr, 0.0f, false, false, false}; }
+
+// ---- launchers: per kernel template ONE ladder that names its instances and maps the plan onto them; what a launch does not
+// use stays null / empty in its argument struct ----
 // The dynamic-LDS limit of a kernel is raised once per process and size (per device: the attribute lives with the loaded code
 // object; a second device in the same process raises its own on first use) instead of in front of every launch (measured: ~0.3 us
 // each on this stack, twelve per step -- nothing a step's timing shows).
@@ -2630,368 +2720,225 @@ void raise_lds_limit(size_t lds) {
     static thread_local size_t granted[16] = {};
     howl_raise_lds(reinterpret_cast<const void*>(Kernel), lds, granted, "res8 kernel");   // refused: reported by HOWL_CHECK_LAUNCH
 }
+// only the row-strip instances (HALO = 2) read the strip geometry
+template <int HALO>
+StripGeom geom_arg(const Res8Plan& p) { return HALO == 2 ? p.sg : StripGeom{1, 1, 0}; }
 
-template <int MODE, int SLICES, int HALO = 0>
-void launch_conv3x3_inst(int nblk, size_t lds, hipStream_t stream, const StageCfg& in, const float* in_stats, const float* wp,
-                         const float* res, float* out, const float* xs, const float* xs_stats, float* part, int B, int H,
-                         const BnFold& fold, const BwdFold& bfold, float* pool, const WFold& wf,
-                         const StripGeom& sg = StripGeom{1, 1, 0}) {
-    raise_lds_limit<conv3x3_mfma_kernel<MODE, SLICES, HALO>>(lds);
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<MODE, SLICES, HALO>), dim3(launch_blocks(nblk, SLICES)), dim3(CONV_THREADS), lds, stream, with_probe(in),
-                       in_stats, wp, res, out, xs, xs_stats, part, pool, B, H, nblk, fold, bfold, wf, sg);
+struct Conv3x3Launch {      // conv3x3_mfma_kernel: MODE 0 = a forward layer, MODE 1 = a data gradient on its own
+    StageCfg in;
+    const float* in_stats = nullptr;
+    const float* wp = nullptr;
+    const float* res = nullptr;
+    float* out = nullptr;
+    const float* xs = nullptr;
+    const float* xs_stats = nullptr;
+    float* part = nullptr;
+    float* pool = nullptr;
+    BnFold fold{};
+    BwdFold bfold{};
+    WFold wf{nullptr, 0, nullptr};
+};
+template <int MODE, int SLICES, int HALO>
+void launch_conv3x3_inst(const Res8Plan& p, hipStream_t stream, const Conv3x3Launch& a) {
+    const int nblk = MODE == 0 ? p.G : p.Gh;
+    raise_lds_limit<conv3x3_mfma_kernel<MODE, SLICES, HALO>>(p.lds_conv);
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<MODE, SLICES, HALO>), dim3(launch_blocks(nblk, SLICES)), dim3(CONV_THREADS), p.lds_conv,
+                       stream, a.in, a.in_stats, a.wp, a.res, a.out, a.xs, a.xs_stats, a.part, a.pool, p.Bv, p.Hs, nblk, a.fold,
+                       a.bfold, a.wf, geom_arg<HALO>(p));
 }
 template <int MODE>
-void launch_conv3x3(int slices, int nblk, size_t lds, hipStream_t stream, const StageCfg& in, const float* in_stats, const float* wp,
-                    const float* res, float* out, const float* xs, const float* xs_stats, float* part, int B, int H,
-                    const BnFold& fold, const BwdFold& bfold = BwdFold{}, float* pool = nullptr,
-                    const WFold& wf = WFold{nullptr, 0, nullptr}, int halo = 0, const StripGeom& sg = StripGeom{1, 1, 0}) {
-    if (halo == 2)      // row (and column) strips of a long map: StripGeom
-        launch_conv3x3_inst<MODE, 1, 2>(nblk, lds, stream, in, in_stats, wp, res, out, xs, xs_stats, part, B, H, fold, bfold, pool, wf, sg);
-    else if (halo == 1)      // strips of a wide map (NUM_MELS = 80): one workgroup per strip, no position slicing
-        launch_conv3x3_inst<MODE, 1, 1>(nblk, lds, stream, in, in_stats, wp, res, out, xs, xs_stats, part, B, H, fold, bfold, pool, wf);
+void launch_conv3x3(const Res8Plan& p, hipStream_t stream, const Conv3x3Launch& a) {
+    const int slices = MODE == 0 ? p.SL : p.SD;
+    if (p.halo == 2)      // row (and column) strips of a long map: StripGeom
+        launch_conv3x3_inst<MODE, 1, 2>(p, stream, a);
+    else if (p.halo == 1)      // strips of a wide map (NUM_MELS = 80): one workgroup per strip, no position slicing
+        launch_conv3x3_inst<MODE, 1, 1>(p, stream, a);
     else if (slices == 4)
-        launch_conv3x3_inst<MODE, 4>(nblk, lds, stream, in, in_stats, wp, res, out, xs, xs_stats, part, B, H, fold, bfold, pool, wf);
+        launch_conv3x3_inst<MODE, 4, 0>(p, stream, a);
     else if (slices == 2)
-        launch_conv3x3_inst<MODE, 2>(nblk, lds, stream, in, in_stats, wp, res, out, xs, xs_stats, part, B, H, fold, bfold, pool, wf);
+        launch_conv3x3_inst<MODE, 2, 0>(p, stream, a);
     else
-        launch_conv3x3_inst<MODE, 1>(nblk, lds, stream, in, in_stats, wp, res, out, xs, xs_stats, part, B, H, fold, bfold, pool, wf);
+        launch_conv3x3_inst<MODE, 1, 0>(p, stream, a);
 }
-template <int SW, int HALO = 0>
-void launch_wgrad_inst(int nblk, size_t lds, hipStream_t stream, const StageCfg& zc, const BwdFold& bfold, const float* s_prev,
-                       const float* in_stats, float* wpart, int B, int H, const StripGeom& sg = StripGeom{1, 1, 0}) {
-    raise_lds_limit<wgrad_mfma_kernel<SW, HALO>>(lds);
-    hipLaunchKernelGGL((wgrad_mfma_kernel<SW, HALO>), dim3(launch_blocks(nblk, SW)), dim3(CONV_THREADS), lds, stream,
-                       WStage{with_probe(zc), s_prev, false}, in_stats, bfold, wpart, B, H, nblk, sg);
+
+struct BwdLayerLaunch {      // bwd_pair_kernel, or its two halves conv3x3_mfma_kernel<1> + wgrad_mfma_kernel
+    StageCfg zc;
+    BwdFold bfold;
+    const float* wp;
+    float* dx;
+    const float* xs;
+    const float* xs_stats;
+    float* spart;
+    const float* s_prev;
+    const float* in_stats;
+    float* wpart;
+    WFold wf;
+};
+template <int SD, int SW, int HALO>
+void launch_pair_inst(const Res8Plan& p, hipStream_t stream, const BwdLayerLaunch& a) {
+    raise_lds_limit<bwd_pair_kernel<SD, SW, HALO>>(p.lds_pair);
+    hipLaunchKernelGGL((bwd_pair_kernel<SD, SW, HALO>), dim3(launch_blocks(p.Gh, SD + SW)), dim3(CONV_THREADS), p.lds_pair, stream, a.zc,
+                       a.bfold, a.wp, a.dx, a.xs, a.xs_stats, a.spart, a.s_prev, a.in_stats, a.wpart, p.Bv, p.Hs, p.Gh, a.wf,
+                       geom_arg<HALO>(p));
 }
-template <int SD, int SW, int HALO = 0>
-void launch_pair_inst(int nblk, size_t lds, hipStream_t stream, const StageCfg& zc, const BwdFold& bfold, const float* wp, float* dx,
-                      const float* xs, const float* xs_stats, float* spart, const float* s_prev, const float* in_stats, float* wpart,
-                      int B, int H, const WFold& wf, const StripGeom& sg = StripGeom{1, 1, 0}) {
-    raise_lds_limit<bwd_pair_kernel<SD, SW, HALO>>(lds);
-    hipLaunchKernelGGL((bwd_pair_kernel<SD, SW, HALO>), dim3(launch_blocks(nblk, SD + SW)), dim3(CONV_THREADS), lds, stream, with_probe(zc), bfold, wp,
-                       dx, xs, xs_stats, spart, s_prev, in_stats, wpart, B, H, nblk, wf, sg);
-}
-void launch_pair(int sd, int sw, int nblk, size_t lds, hipStream_t stream, const StageCfg& zc, const BwdFold& bfold, const float* wp,
-                 float* dx, const float* xs, const float* xs_stats, float* spart, const float* s_prev, const float* in_stats,
-                 float* wpart, int B, int H, const WFold& wf, int halo = 0, const StripGeom& sg = StripGeom{1, 1, 0}) {
-    if (halo == 2)
-        launch_pair_inst<1, 1, 2>(nblk, lds, stream, zc, bfold, wp, dx, xs, xs_stats, spart, s_prev, in_stats, wpart, B, H, wf, sg);
-    else if (halo == 1)
-        launch_pair_inst<1, 1, 1>(nblk, lds, stream, zc, bfold, wp, dx, xs, xs_stats, spart, s_prev, in_stats, wpart, B, H, wf);
-    else if (sd == 4 && sw == 2)
-        launch_pair_inst<4, 2>(nblk, lds, stream, zc, bfold, wp, dx, xs, xs_stats, spart, s_prev, in_stats, wpart, B, H, wf);
-    else if (sd == 2 && sw == 2)
-        launch_pair_inst<2, 2>(nblk, lds, stream, zc, bfold, wp, dx, xs, xs_stats, spart, s_prev, in_stats, wpart, B, H, wf);
-    else if (sd == 2 && sw == 1)
-        launch_pair_inst<2, 1>(nblk, lds, stream, zc, bfold, wp, dx, xs, xs_stats, spart, s_prev, in_stats, wpart, B, H, wf);
+void launch_pair(const Res8Plan& p, hipStream_t stream, const BwdLayerLaunch& a) {
+    if (p.halo == 2)
+        launch_pair_inst<1, 1, 2>(p, stream, a);
+    else if (p.halo == 1)
+        launch_pair_inst<1, 1, 1>(p, stream, a);
+    else if (p.SD == 4 && p.SW == 2)
+        launch_pair_inst<4, 2, 0>(p, stream, a);
+    else if (p.SD == 2 && p.SW == 2)
+        launch_pair_inst<2, 2, 0>(p, stream, a);
+    else if (p.SD == 2 && p.SW == 1)
+        launch_pair_inst<2, 1, 0>(p, stream, a);
     else
-        launch_pair_inst<1, 1>(nblk, lds, stream, zc, bfold, wp, dx, xs, xs_stats, spart, s_prev, in_stats, wpart, B, H, wf);
+        launch_pair_inst<1, 1, 0>(p, stream, a);
+}
+template <int SW, int HALO>
+void launch_wgrad_inst(const Res8Plan& p, hipStream_t stream, const BwdLayerLaunch& a) {
+    StageCfg zw = a.zc;
+    zw.ds = nullptr;      // the skip gradient ds_i is the data gradient's to write
+    raise_lds_limit<wgrad_mfma_kernel<SW, HALO>>(p.lds_wgrad);
+    hipLaunchKernelGGL((wgrad_mfma_kernel<SW, HALO>), dim3(launch_blocks(p.Gh, SW)), dim3(CONV_THREADS), p.lds_wgrad, stream,
+                       WStage{zw, a.s_prev, false}, a.in_stats, a.bfold, a.wpart, p.Bv, p.Hs, p.Gh, geom_arg<HALO>(p));
+}
+void launch_wgrad(const Res8Plan& p, hipStream_t stream, const BwdLayerLaunch& a) {
+    if (p.halo == 2)
+        launch_wgrad_inst<1, 2>(p, stream, a);
+    else if (p.halo == 1)
+        launch_wgrad_inst<1, 1>(p, stream, a);
+    else if (p.SW == 2)      // (no strips: Bv = B, which is what these two instances were always given)
+        launch_wgrad_inst<2, 0>(p, stream, a);
+    else
+        launch_wgrad_inst<1, 0>(p, stream, a);
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t howl_res8_workspace_bytes(int B, int T) { return howl_res8_workspace_bytes_mels(B, T, 40); }
-
-size_t howl_res8_workspace_bytes_mels(int B, int T, int M) {
-    const Strips sp = strips_for(B, T, M);
-    return ws_layout(nullptr, nullptr, sp.Bv, sp.Hs, even_grid(conv_grid(sp.Bv), sp.ns));
+struct Feat {      // log-mel input, element (b, t, m) at x[b * sb + t * st + m * sm]
+    const float* x;
+    long sb, st, sm;
+};
+// conv0 + ReLU + AvgPool(3,4) into s0 / mask0; the launch's extra blocks pack the six layers' weights for both directions
+template <int NS, bool EXACT>
+void launch_conv0_fwd_inst(const Res8Plan& p, hipStream_t stream, const Feat& f, const HowlRes8Params* prm, float* s0,
+                           unsigned short* mask0) {
+    const int npack = (2 * 6 * PACK_ELEMS + C0M_THREADS - 1) / C0M_THREADS;
+    hipLaunchKernelGGL((conv0_fwd_mfma_kernel<NS, EXACT>), dim3(p.G0 + npack), dim3(C0M_THREADS), p.lds_conv0, stream, f.x, f.sb, f.st,
+                       f.sm, prm->conv0_w, s0, mask0, p.Bw, p.Tw, p.M, p.Hs, p.G0, ptrs6(prm->conv_w), p.ws.wp_fwd, p.ws.wp_bwd,
+                       p.c0_nwin, p.c0_step, p.c0_last, p.S0);
+}
+void launch_conv0_fwd(const Res8Plan& p, hipStream_t stream, const Feat& f, const HowlRes8Params* prm, float* s0,
+                      unsigned short* mask0) {
+    if (p.c0_exact && p.ns == 2)
+        launch_conv0_fwd_inst<2, true>(p, stream, f, prm, s0, mask0);
+    else if (p.c0_exact)
+        launch_conv0_fwd_inst<1, true>(p, stream, f, prm, s0, mask0);
+    else if (p.ns == 2)
+        launch_conv0_fwd_inst<2, false>(p, stream, f, prm, s0, mask0);
+    else
+        launch_conv0_fwd_inst<1, false>(p, stream, f, prm, s0, mask0);
+}
+template <int NS, bool EXACT>
+void launch_conv0_wgrad_inst(const Res8Plan& p, hipStream_t stream, const Feat& f, const unsigned short* mask0, const float* g0) {
+    hipLaunchKernelGGL((conv0_wgrad_valu_kernel<NS, EXACT>), dim3(p.G0w), dim3(C0G_THREADS), p.lds_conv0w, stream, f.x, f.sb, f.st, f.sm,
+                       mask0, g0, (const float*)nullptr, p.ws.c0part, p.B, p.Tw, p.M, p.Hs, p.S0w, p.sg, p.T);
+}
+void launch_conv0_wgrad(const Res8Plan& p, hipStream_t stream, const Feat& f, const unsigned short* mask0, const float* g0) {
+    if (p.c0_exact && p.ns == 2)
+        launch_conv0_wgrad_inst<2, true>(p, stream, f, mask0, g0);
+    else if (p.c0_exact)
+        launch_conv0_wgrad_inst<1, true>(p, stream, f, mask0, g0);
+    else if (p.ns == 2)
+        launch_conv0_wgrad_inst<2, false>(p, stream, f, mask0, g0);
+    else
+        launch_conv0_wgrad_inst<1, false>(p, stream, f, mask0, g0);
 }
 
-size_t howl_res8_eval_workspace_bytes_mels(int B, int T, int M) {
-    const Strips sp = strips_for(B, T, M);
-    size_t eval_bytes = 0;
-    ws_layout(nullptr, nullptr, sp.Bv, sp.Hs, even_grid(conv_grid(sp.Bv), sp.ns), &eval_bytes);
-    return eval_bytes;
-}
-
-int howl_res8_row_strips(int T) { return strips_for(1, T, 40).nr; }
-
-size_t howl_res8_saved_floats(int B, int T, int M) {
-    const Strips sp = strips_for(B, T, M);
-    return (size_t)sp.Bv * NMAP * sp.Hs * PW;
-}
-
-}  // extern "C"
-
-namespace {
 // howl_res8_fwd, optionally with the cross-entropy of the step in its last launch (labels != nullptr: see head_fwd_kernel)
-int res8_fwd_impl(const HowlRes8Params* prm, const float* feat, long sb, long st, long sm, int B, int T, int M, int C,
-                  int training, const HowlRes8Saved* sv, float* logits, void* ws, size_t ws_bytes, const long long* labels,
-                  float* nll, float* dlogits, hipStream_t stream) {
-    HOWL_REQUIRE(prm && feat && sv && logits && ws, "howl_res8_fwd: null pointer");
+int res8_fwd_impl(const HowlRes8Params* prm, const Feat& feat, int B, int T, int M, int C, int training, const HowlRes8Saved* sv,
+                  float* logits, void* ws, size_t ws_bytes, const long long* labels, float* nll, float* dlogits, hipStream_t stream) {
+    HOWL_REQUIRE(prm && feat.x && sv && logits && ws, "howl_res8_fwd: null pointer");
     HOWL_REQUIRE(labels == nullptr || (nll != nullptr && dlogits != nullptr && C <= HEAD_XC),
                  "howl_res8_fwd_xent: nll / dlogits missing or more than %d classes (C=%d)", HEAD_XC, C);
     HOWL_REQUIRE(mel_strips(M) > 0, "howl_res8_fwd: res8 pools (3,4) over 40 or 80 mel bins; got M=%d", M);
-    const int Ht = T / 3;         // pooled rows of the whole map
-    HOWL_REQUIRE(B >= 1 && Ht >= 1, "howl_res8_fwd: B=%d T=%d unsupported (T >= 3)", B, T);
+    HOWL_REQUIRE(B >= 1 && T / 3 >= 1, "howl_res8_fwd: B=%d T=%d unsupported (T >= 3)", B, T);
     HOWL_REQUIRE(C >= 1, "howl_res8_fwd: C must be positive");
-    // wide maps: every utterance is NS strips of 10 pooled columns (HaloSlot); long maps: NR row strips of H rows each (StripGeom);
-    // every strip is a block of the (Bv, 45, H, 10) activations
-    const Strips sp = strips_for(B, T, M);
-    HOWL_REQUIRE(sp.hv_last >= 1 && sp.nr <= MAX_ROW_STRIPS, "howl_res8_fwd: T=%d frames unsupported (%d row strips)", T, sp.nr);
-    const int NS = sp.ns, H = sp.Hs, Bv = sp.Bv, halo = sp.halo;
-    const bool grid = halo == 2;
-    const int G = even_grid(conv_grid(Bv), NS);
-    Ws w;
-    size_t need_eval = 0;
-    const size_t need_train = ws_layout(&w, static_cast<char*>(ws), Bv, H, G, &need_eval);
+    // wide maps: every utterance is ns strips of 10 pooled columns (HaloSlot); long maps: nr row strips of Hs rows each (StripGeom);
+    // every strip is a block of the (Bv, 45, Hs, 10) activations
+    const Res8Plan p = res8_plan(B, T, M, ws);
+    HOWL_REQUIRE(p.hv_last >= 1 && p.nr <= MAX_ROW_STRIPS, "howl_res8_fwd: T=%d frames unsupported (%d row strips)", T, p.nr);
     // eval mode touches nothing behind the pooled sums (howl_res8_eval_workspace_bytes_mels), and reads s[i-1], s[i-2] while it
     // writes s[i]: the caller may pass three activation buffers in rotation (s[i] = buffer i mod 3) instead of seven
-    const size_t need = training ? need_train : need_eval;
-    if (ws_bytes < need) {
-        howl_set_error("howl_res8_fwd: workspace %zu < %zu bytes", ws_bytes, need);
-        return HOWL_E_WORKSPACE;
-    }
-    const int P = H * PW;
-    const int Pt = Ht * PW * NS;      // positions of one utterance's whole map
-    HowlPtrs6 cw, rm, rv;
-    for (int i = 0; i < 6; ++i) {
-        cw.p[i] = const_cast<float*>(prm->conv_w[i]);
-        rm.p[i] = prm->bn_running_mean[i];
-        rv.p[i] = prm->bn_running_var[i];
-    }
-    if (!training) hipLaunchKernelGGL(bn_eval_stats_kernel, dim3(6), dim3(64), 0, stream, rm, rv, sv->bn_stats);
-
-    // conv0 sees an utterance (or, for row strips, its NR windows of 3 H frames with the clip's real frames on both sides)
-    const int Bw = B * sp.nr, Tw = grid ? 3 * H : T;
-    const size_t l0 = conv0_tile_floats(Tw, M) * sizeof(float);
-    // 103 VGPRs and 15 KB of LDS: two workgroups per CU overlap one's tile load / stores with the other's MFMAs
-    const int S0 = conv0_slices(Bw);
-    const int G0 = Bw * S0 < 2 * howl_num_cus() ? Bw * S0 : 2 * howl_num_cus();
+    if (int rc = check_workspace("howl_res8_fwd", ws_bytes, training ? p.train_bytes : p.eval_bytes)) return rc;
+    const Ws& w = p.ws;
+    if (!training)
+        hipLaunchKernelGGL(bn_eval_stats_kernel, dim3(6), dim3(64), 0, stream, ptrs6(prm->bn_running_mean), ptrs6(prm->bn_running_var),
+                           sv->bn_stats);
     {
         HowlProfScope prof("conv0_fwd", stream);
-        const int npack = (2 * 6 * PACK_ELEMS + C0M_THREADS - 1) / C0M_THREADS;
-#define HOWL_CONV0_FWD(NS_, EX_)                                                                                                  \
-    hipLaunchKernelGGL((conv0_fwd_mfma_kernel<NS_, EX_>), dim3(G0 + npack), dim3(C0M_THREADS), l0, stream, feat, sb, st, sm,       \
-                       prm->conv0_w, sv->s[0], sv->mask0, Bw, Tw, M, H, G0, cw, w.wp_fwd, w.wp_bwd, grid ? sp.nr : 1,             \
-                       grid ? 3 * H : 0, grid ? T : 0, S0)
-        if (grid && NS == 2)
-            HOWL_CONV0_FWD(2, true);
-        else if (grid)
-            HOWL_CONV0_FWD(1, true);
-        else if (NS == 2)
-            HOWL_CONV0_FWD(2, false);
-        else
-            HOWL_CONV0_FWD(1, false);
-#undef HOWL_CONV0_FWD
+        launch_conv0_fwd(p, stream, feat, prm, sv->s[0], sv->mask0);
     }
-    const size_t lc = conv_lds_bytes(H, grid);
-    const double count = (double)B * (double)Pt;
-    const int SL = halo != 0 ? 1 : conv_slices(G, H, howl_num_cus());
+    const double count = (double)B * (double)p.Pt;
     // Training: layer i leaves its statistics as per-workgroup partials; layer i+1 folds them in its own prologue (BnFold),
     // so only the last layer needs the stand-alone finalize.  The partial buffers alternate between layers.
+    const auto fold_of = [&](int layer, float* part) {      // BatchNorm `layer`'s partials -> its statistics and running buffers
+        return BnFold{part, p.G * p.SL, count, sv->bn_stats + (size_t)(layer - 1) * 2 * CP,
+                      HowlBnBuffers{prm->bn_running_mean[layer - 1], prm->bn_running_var[layer - 1], prm->bn_num_batches[layer - 1]}};
+    };
     for (int i = 1; i <= 6; ++i) {
-        const bool even = (i % 2) == 0;
-        const float* res = even ? sv->s[i - 2] : nullptr;
-        float* part_out = training ? ((i & 1) ? w.part : w.part2) : (float*)nullptr;
-        BnFold fold{};
-        const float* in_stats = nullptr;
-        if (i > 1) {
-            if (training)
-                fold = BnFold{(i & 1) ? w.part2 : w.part, G * SL, count, sv->bn_stats + (size_t)(i - 2) * 2 * CP,
-                              HowlBnBuffers{prm->bn_running_mean[i - 2], prm->bn_running_var[i - 2], prm->bn_num_batches[i - 2]}};
-            else
-                in_stats = sv->bn_stats + (size_t)(i - 2) * 2 * CP;
-        }
-        {
-            HowlProfScope prof("conv3x3_fwd", stream);
-            launch_conv3x3<0>(SL, G, lc, stream, plain_tile(sv->s[i - 1]), in_stats, w.wp_fwd + (size_t)(i - 1) * 3 * KSTEPS * 64, res, sv->s[i],
-                              nullptr, nullptr, part_out, Bv, H, fold, BwdFold{}, i == 6 ? w.pool : (float*)nullptr,
-                              WFold{nullptr, 0, nullptr}, halo, sp.sg);
-        }
+        Conv3x3Launch a;
+        a.in = plain_tile(sv->s[i - 1]);
+        a.wp = w.wp_fwd + (size_t)(i - 1) * 3 * KSTEPS * 64;
+        a.res = (i % 2) == 0 ? sv->s[i - 2] : nullptr;
+        a.out = sv->s[i];
+        a.part = training ? ((i & 1) ? w.part : w.part2) : nullptr;
+        a.pool = i == 6 ? w.pool : nullptr;
+        if (i > 1 && training)
+            a.fold = fold_of(i - 1, (i & 1) ? w.part2 : w.part);
+        else if (i > 1)
+            a.in_stats = sv->bn_stats + (size_t)(i - 2) * 2 * CP;
+        HowlProfScope prof("conv3x3_fwd", stream);
+        launch_conv3x3<0>(p, stream, a);
     }
     // (training: the head folds BatchNorm 6's statistics itself -- no one-block finalize launch in between)
-    const BnFold hfold = training ? BnFold{w.part2, G * SL, count, sv->bn_stats + (size_t)5 * 2 * CP,
-                                           HowlBnBuffers{prm->bn_running_mean[5], prm->bn_running_var[5], prm->bn_num_batches[5]}}
-                                  : BnFold{};
     // the spatial mean runs over all strips of an utterance: nr * ns blocks of 4 SL position groups, Pt positions
+    const int groups = 4 * p.SL;
     hipLaunchKernelGGL(head_fwd_kernel, dim3(B < 1024 ? B : 1024), dim3(HEAD_THREADS), 0, stream, sv->s[6],
-                       sv->bn_stats + (size_t)5 * 2 * CP, prm->out_w, prm->out_b, sv->pooled, logits, B, Pt, C, labels, nll, dlogits,
-                       w.dpool, 1.0f / (float)B, (const float*)w.pool, 4 * SL, 4 * SL < (P + 15) / 16 ? 4 * SL : (P + 15) / 16, hfold,
-                       sp.nr * NS);
+                       sv->bn_stats + (size_t)5 * 2 * CP, prm->out_w, prm->out_b, sv->pooled, logits, B, p.Pt, C, labels, nll, dlogits,
+                       w.dpool, 1.0f / (float)B, (const float*)w.pool, groups, groups < (p.P + 15) / 16 ? groups : (p.P + 15) / 16,
+                       training ? fold_of(6, w.part2) : BnFold{}, p.nr * p.ns);
     HOWL_CHECK_LAUNCH("howl_res8_fwd");
     return HOWL_OK;
 }
-}  // namespace
 
-extern "C" {
-
-int howl_res8_fwd(const HowlRes8Params* prm, const float* feat, long sb, long st, long sm, int B, int T, int M, int C,
-                  int training, const HowlRes8Saved* sv, float* logits, void* ws, size_t ws_bytes, hipStream_t stream) {
-    return res8_fwd_impl(prm, feat, sb, st, sm, B, T, M, C, training, sv, logits, ws, ws_bytes, nullptr, nullptr, nullptr, stream);
-}
-
-int howl_res8_fwd_xent(const HowlRes8Params* prm, const float* feat, long sb, long st, long sm, int B, int T, int M, int C,
-                       const HowlRes8Saved* sv, const long long* labels, float* logits, float* nll, float* dlogits, void* ws,
-                       size_t ws_bytes, hipStream_t stream) {
-    HOWL_REQUIRE(labels && nll && dlogits, "howl_res8_fwd_xent: null pointer");
-    return res8_fwd_impl(prm, feat, sb, st, sm, B, T, M, C, 1, sv, logits, ws, ws_bytes, labels, nll, dlogits, stream);
-}
-
-// ---- long inputs (eval mode) --------------------------------------------------------------------------------------------------
-// The kernels keep one utterance's whole (45, H, 10) map in LDS, H <= 27 pooled rows (83 frames).  A longer clip is cut into
-// windows of 27 pooled rows that overlap by 14: the six 3x3 convolutions (and conv0's own frame) spread a window's zero
-// padding 7 rows inwards, so a window's rows [7, 20) -- [0, 20) for the first, [7, 27) for the last -- are exactly what the
-// unbounded convolution stack computes, and those ranges tile the clip.  Inference statistics are per channel constants,
-// so nothing couples the windows except the final spatial mean.  (Training on such windows would need BatchNorm batch
-// statistics over the de-duplicated rows: not offered; the reference's training windows are <= 1 s.)
-namespace {
-constexpr int WIN_H = MAX_H, WIN_MARGIN = 7, WIN_STEP = WIN_H - 2 * WIN_MARGIN;   // 27, 7, 13
-int long_windows(int H) { return H <= WIN_H ? 1 : (H - WIN_H + WIN_STEP - 1) / WIN_STEP + 1; }
-}  // namespace
-
-size_t howl_res8_long_workspace_bytes(int B, int T) { return howl_res8_long_workspace_bytes_mels(B, T, 40); }
-
-size_t howl_res8_long_workspace_bytes_mels(int B, int T, int M) {
-    const int H = T / 3, nw = long_windows(H);
-    const size_t Bv = (size_t)B * nw * (mel_strips(M) > 0 ? mel_strips(M) : 1);
-    // three rotating activation maps + eval statistics + the regular workspace of the virtual batch
-    static_assert((6 * 2 * CP * sizeof(float)) % 256 == 0, "statistics block keeps the 256-byte alignment");
-    return 3 * (((Bv * NMAP * WIN_H * PW * sizeof(float)) + 255) / 256 * 256) + 6 * 2 * CP * sizeof(float) + 256 +
-           ws_layout(nullptr, nullptr, (int)Bv, WIN_H, even_grid(conv_grid((int)Bv), mel_strips(M)));
-}
-
-int howl_res8_fwd_long(const HowlRes8Params* prm, const float* feat, long sb, long st, long sm, int B, int T, int M, int C,
-                       float* logits, void* ws, size_t ws_bytes, hipStream_t stream) {
-    HOWL_REQUIRE(prm && feat && logits && ws, "howl_res8_fwd_long: null pointer");
-    const int NS = mel_strips(M);
-    HOWL_REQUIRE(NS > 0, "howl_res8_fwd_long: res8 pools (3,4) over 40 or 80 mel bins; got M=%d", M);
-    const int H = T / 3;
-    HOWL_REQUIRE(B >= 1 && H > WIN_H && C >= 1, "howl_res8_fwd_long: for T > 83 frames (got B=%d T=%d); shorter inputs use howl_res8_fwd", B, T);
-    const int nw = long_windows(H);
-    HOWL_REQUIRE(nw <= MAX_WINDOWS, "howl_res8_fwd_long: T=%d needs %d windows (max %d)", T, nw, MAX_WINDOWS);
-    if (ws_bytes < howl_res8_long_workspace_bytes_mels(B, T, M)) {
-        howl_set_error("howl_res8_fwd_long: workspace %zu < %zu bytes", ws_bytes, howl_res8_long_workspace_bytes_mels(B, T, M));
-        return HOWL_E_WORKSPACE;
-    }
-    // T % 3 trailing frames take no part in the pooling but are conv0's neighbours of the clip's last frame: every window
-    // reads them too (inner windows simply see real samples there instead of padding, inside their discarded margin)
-    // Bw windows, each NS strips of 10 pooled columns (wide maps: HaloSlot): Bv blocks of (45, WIN_H, 10)
-    const int Bw = B * nw, Bv = Bw * NS, Tw = 3 * WIN_H + T % 3, P = WIN_H * PW;
-    const bool halo = NS > 1;
-    const size_t act = ((size_t)Bv * NMAP * P * sizeof(float) + 255) / 256 * 256;
-    char* base = static_cast<char*>(ws);
-    float* buf[3] = {reinterpret_cast<float*>(base), reinterpret_cast<float*>(base + act), reinterpret_cast<float*>(base + 2 * act)};
-    float* stats = reinterpret_cast<float*>(base + 3 * act);
-    Ws w;
-    const int G = even_grid(conv_grid(Bv), NS);
-    ws_layout(&w, base + 3 * act + 6 * 2 * CP * sizeof(float) + 256, Bv, WIN_H, G);
-    HowlWinRows rows;
-    for (int i = 0; i < nw; ++i) {
-        const int a = i * WIN_STEP < H - WIN_H ? i * WIN_STEP : H - WIN_H;          // first pooled row of window i
-        const int a_next = (i + 1) * WIN_STEP < H - WIN_H ? (i + 1) * WIN_STEP : H - WIN_H;
-        const int g_lo = i == 0 ? 0 : a + WIN_MARGIN;                              // clip rows [g_lo, g_hi) come from window i
-        const int g_hi = i == nw - 1 ? H : a_next + WIN_MARGIN;
-        rows.lo[i] = g_lo - a;
-        rows.hi[i] = g_hi - a;
-    }
-    HowlPtrs6 cw, rm, rv;
-    for (int i = 0; i < 6; ++i) {
-        cw.p[i] = const_cast<float*>(prm->conv_w[i]);
-        rm.p[i] = prm->bn_running_mean[i];
-        rv.p[i] = prm->bn_running_var[i];
-    }
-    hipLaunchKernelGGL(bn_eval_stats_kernel, dim3(6), dim3(64), 0, stream, rm, rv, stats);
-    const size_t l0 = conv0_tile_floats(Tw, M) * sizeof(float);
-    const int G0 = Bw < 2 * howl_num_cus() ? Bw : 2 * howl_num_cus();
-    const int npack = (2 * 6 * PACK_ELEMS + C0M_THREADS - 1) / C0M_THREADS;
-    if (halo)
-        hipLaunchKernelGGL(conv0_fwd_mfma_kernel<2>, dim3(G0 + npack), dim3(C0M_THREADS), l0, stream, feat, sb, st, sm, prm->conv0_w,
-                           buf[0], (unsigned short*)nullptr, Bw, Tw, M, WIN_H, G0, cw, w.wp_fwd, w.wp_bwd, nw, 3 * WIN_STEP,
-                           3 * (H - WIN_H), 1);
-    else
-        hipLaunchKernelGGL(conv0_fwd_mfma_kernel<1>, dim3(G0 + npack), dim3(C0M_THREADS), l0, stream, feat, sb, st, sm, prm->conv0_w,
-                           buf[0], (unsigned short*)nullptr, Bw, Tw, M, WIN_H, G0, cw, w.wp_fwd, w.wp_bwd, nw, 3 * WIN_STEP,
-                           3 * (H - WIN_H), 1);
-    const size_t lc = conv_lds_bytes(WIN_H);
-    const int SL = halo ? 1 : conv_slices(G, WIN_H, howl_num_cus());
-    // x_i lives in buf[cur]; even layers add the map two layers back (kept in buf[skip])
-    int cur = 0, skip = 0;
-    for (int i = 1; i <= 6; ++i) {
-        const bool even = (i % 2) == 0;
-        int out = 0;
-        while (out == cur || out == skip) ++out;
-        launch_conv3x3<0>(SL, G, lc, stream, plain_tile(buf[cur]), i == 1 ? (const float*)nullptr : (const float*)(stats + (size_t)(i - 2) * 2 * CP),
-                          w.wp_fwd + (size_t)(i - 1) * 3 * KSTEPS * 64, even ? (const float*)buf[skip] : (const float*)nullptr, buf[out],
-                          nullptr, nullptr, nullptr, Bv, WIN_H, BnFold{}, BwdFold{}, nullptr, WFold{nullptr, 0, nullptr}, halo);
-        if (even) skip = out;      // s_i (i even) is the next residual source; s_0 is the first one
-        cur = out;
-    }
-    hipLaunchKernelGGL(head_fwd_windows_kernel, dim3(B < 1024 ? B : 1024), dim3(256), 0, stream, (const float*)buf[cur],
-                       (const float*)(stats + (size_t)5 * 2 * CP), prm->out_w, prm->out_b, logits, B, nw, WIN_H, rows,
-                       1.0f / ((float)H * PW * NS), C, NS);
-    HOWL_CHECK_LAUNCH("howl_res8_fwd_long");
-    return HOWL_OK;
-}
-
-// part 0: the whole backward pass.  Data-parallel steps call it in two parts so that the gradient all-reduce of everything
-// but conv0 runs under conv0's weight gradient: part 1 = head + layers 6..1 (data and weight gradients) + the fold of the six
-// layers' weight-gradient partials -- after it gr->conv_w[0..5], gr->out_w, gr->out_b are final; part 2 = conv0's weight
-// gradient and its fold (gr->conv0_w).  The two parts of a pass must be called in order with identical arguments.
-}  // extern "C"
-
-namespace {
 // howl_res8_bwd_part; with nll != nullptr the pass follows howl_res8_fwd_xent: the pooled gradient is already in the workspace
-// and the batch mean of nll goes to `loss` (one more block of the head's parameter-gradient launch)
-int res8_bwd_impl(const HowlRes8Params* prm, const float* feat, long sb, long st, long sm, int B, int T, int M, int C,
-                  const HowlRes8Saved* sv, const float* dlogits, const HowlRes8Grads* gr, void* ws, size_t ws_bytes,
-                  int part, const float* nll, float* loss, hipStream_t stream, const HowlAdamW* adamw = nullptr) {
-    HOWL_REQUIRE(prm && feat && sv && dlogits && gr && ws, "howl_res8_bwd: null pointer");
+// and the batch mean of nll goes to `loss` (one more block of the head's parameter-gradient launch).
+// Per layer  bn_relu_bwd -> [dgrad || wgrad in one launch, half the CUs each] -> bn_bwd_finalize, all on the caller's stream; every
+// layer's weight-gradient partials stay in the workspace and ONE launch reduces them all at the end (nothing but AdamW waits for them).
+int res8_bwd_impl(const HowlRes8Params* prm, const Feat& feat, int B, int T, int M, int C, const HowlRes8Saved* sv, const float* dlogits,
+                  const HowlRes8Grads* gr, void* ws, size_t ws_bytes, int part, const float* nll, float* loss, hipStream_t stream,
+                  const HowlAdamW* adamw = nullptr) {
+    HOWL_REQUIRE(prm && feat.x && sv && dlogits && gr && ws, "howl_res8_bwd: null pointer");
     HOWL_REQUIRE(adamw == nullptr || (part == 0 && adamw->p && adamw->g && adamw->m && adamw->v && adamw->n >= 1 && adamw->step >= 1),
                  "howl_res8_bwd: HowlAdamW needs the whole pass (part 0) and complete buffers");
     HOWL_REQUIRE(part >= 0 && part <= 2, "howl_res8_bwd_part: part must be 0 (all), 1 or 2");
     const bool run_layers = part != 2, run_conv0 = part != 1;
     HOWL_REQUIRE(mel_strips(M) > 0, "howl_res8_bwd: M must be 40 or 80 (got %d)", M);
-    const int Ht = T / 3;
-    HOWL_REQUIRE(B >= 1 && Ht >= 1, "howl_res8_bwd: B=%d T=%d unsupported", B, T);
-    const Strips sp = strips_for(B, T, M);      // column strips (HaloSlot) x row strips (StripGeom), each a block of the activations
-    HOWL_REQUIRE(sp.hv_last >= 1 && sp.nr <= MAX_ROW_STRIPS, "howl_res8_bwd: T=%d frames unsupported (%d row strips)", T, sp.nr);
-    const int NS = sp.ns, H = sp.Hs, Bv = sp.Bv, halo = sp.halo;
-    const bool grid = halo == 2;
-    const int Pt = Ht * PW * NS;      // positions of one utterance's whole map
-    const int G = even_grid(conv_grid(Bv), NS);
-    Ws w;
-    const size_t need = ws_layout(&w, static_cast<char*>(ws), Bv, H, G);
-    if (ws_bytes < need) {
-        howl_set_error("howl_res8_bwd: workspace %zu < %zu bytes", ws_bytes, need);
-        return HOWL_E_WORKSPACE;
-    }
-    const int P = H * PW;
-    const double count = (double)B * (double)Pt;
-    const size_t act = (size_t)Bv * NMAP * P;
-    HOWL_REQUIRE(act / 2 < (size_t)1 << 31, "howl_res8_bwd: B=%d too large for the 32-bit element index of the elementwise pass", B);
-    int eg = (int)((act / 4 + BRB_THREADS - 1) / BRB_THREADS);      // one 16-byte quad per thread and trip
-    if (eg < 1) eg = 1;
-    if (eg > 2 * howl_num_cus()) eg = 2 * howl_num_cus();
+    HOWL_REQUIRE(B >= 1 && T / 3 >= 1, "howl_res8_bwd: B=%d T=%d unsupported", B, T);
+    const Res8Plan p = res8_plan(B, T, M, ws);      // column strips (HaloSlot) x row strips (StripGeom), each a block of the activations
+    HOWL_REQUIRE(p.hv_last >= 1 && p.nr <= MAX_ROW_STRIPS, "howl_res8_bwd: T=%d frames unsupported (%d row strips)", T, p.nr);
+    if (int rc = check_workspace("howl_res8_bwd", ws_bytes, p.train_bytes)) return rc;
+    HOWL_REQUIRE(p.saved_floats / 2 < (size_t)1 << 31, "howl_res8_bwd: B=%d too large for the 32-bit element index of the elementwise pass", B);
+    const Ws& w = p.ws;
+    const double count = (double)B * (double)p.Pt;
 
     if (run_layers) {
         if (nll == nullptr)
             hipLaunchKernelGGL(head_bwd_pool_kernel, dim3((B * CP + 255) / 256), dim3(256), 0, stream, dlogits, prm->out_w, w.dpool,
                                B, C);
         hipLaunchKernelGGL(head_bwd_param_kernel, dim3(C + (nll != nullptr ? 2 : 1)), dim3(1024), 0, stream, dlogits, sv->pooled,
-                           w.dpool, gr->out_w, gr->out_b, w.m12, B, C, Pt, nll, loss);
+                           w.dpool, gr->out_w, gr->out_b, w.m12, B, C, p.Pt, nll, loss);
     }
-    const size_t lc = conv_lds_bytes(H, grid);
-    const size_t lw = wgrad_lds_bytes(H);
-    const size_t lp = lc > lw ? lc : lw;
-    const char* pair_env = getenv("HOWL_RES8_BWD_PAIR");
-    const bool merged = !(pair_env != nullptr && pair_env[0] == '0');
-    // HOWL_RES8_BWD_FUSED=0: the elementwise BatchNorm / ReLU backward as its own launch per layer (bn_relu_bwd_kernel writes
-    // dz_i, the pair stages it as it is) -- the reference point of the tests; default: built inside the pair's staging
-    const char* fused_env = getenv("HOWL_RES8_BWD_FUSED");
-    const bool fused = halo != 0 || !(fused_env != nullptr && fused_env[0] == '0');   // (strips: the fused staging only)
-    // dgrad and wgrad side by side: half the CUs each
-    const int half = howl_num_cus() / 2 > 0 ? howl_num_cus() / 2 : 1;
-    const int Gh = even_grid(Bv < half ? Bv : half, NS);
-    const size_t wpart_stride = (size_t)Gh * CP * WNCOL;
-    int SD = 1, SW = 1;
-    if (halo == 0) pair_slices(Gh, H, &SD, &SW);
-    // the fold of a layer's weight-gradient partials rides in the NEXT pair launch when that launch has enough data-gradient
-    // workgroups to spread the 9,984 column pairs thin (a single utterance's four workgroups would walk 26 trips of two barriers
-    // each: +60 us at batch 1); small batches keep the one reduction launch at the end
-    const bool fold_in_pair = Gh * SD >= 64;
     float* dx_cur = nullptr;      // gradient w.r.t. the BN output of layer i (nullptr: broadcast of dpool)
     float* dx_next = w.bufa;
     float* ds_prev = nullptr;     // ds_{i+2}
@@ -3003,18 +2950,19 @@ int res8_bwd_impl(const HowlRes8Params* prm, const float* feat, long sb, long st
         float* dz = even ? w.dz : w.dz2;
         // the BatchNorm-backward statistics travel as partials from the data gradient of layer i+1 to the consumer of dx_i; the
         // fused pair reads them in its prologue while its own data-gradient workgroups write theirs at their end: two buffers
-        float* part_in = fused ? ((i & 1) ? w.part2 : w.part) : w.part;
-        float* part_out = fused ? ((i & 1) ? w.part : w.part2) : w.part;
+        float* part_in = p.fused ? ((i & 1) ? w.part2 : w.part) : w.part;
+        float* part_out = p.fused ? ((i & 1) ? w.part : w.part2) : w.part;
+        BwdLayerLaunch a;
         // layer 6 takes its two means from the head (m12); the others fold the partials of the data gradient above them
-        const BwdFold bfold{stats_i, w.m12, i == 6 ? (const float*)nullptr : (const float*)part_in, Gh * SD, count};
-        StageCfg zc = plain_tile(dz);
-        if (fused)
-            zc = StageCfg{dx_cur, sv->s[i], even ? (const float*)ds_prev : (const float*)nullptr, ds_out, w.dpool,
-                          1.0f / (float)Pt, true, even, false};
+        a.bfold = BwdFold{stats_i, w.m12, i == 6 ? (const float*)nullptr : (const float*)part_in, p.Gh * p.SD, count};
+        a.zc = plain_tile(dz);
+        if (p.fused)
+            a.zc = StageCfg{dx_cur, sv->s[i], even ? (const float*)ds_prev : (const float*)nullptr, ds_out, w.dpool,
+                            1.0f / (float)p.Pt, true, even, false};
         else if (run_layers)
-            hipLaunchKernelGGL(bn_relu_bwd_kernel, dim3(eg), dim3(BRB_THREADS), 0, stream, (const float*)dx_cur, w.dpool, sv->s[i],
-                               stats_i, w.m12, bfold.part, Gh * SD, count, even ? (const float*)ds_prev : (const float*)nullptr,
-                               even ? 1 : 0, ds_out, dz, B, P);
+            hipLaunchKernelGGL(bn_relu_bwd_kernel, dim3(p.ew_grid), dim3(BRB_THREADS), 0, stream, (const float*)dx_cur, w.dpool, sv->s[i],
+                               stats_i, w.m12, a.bfold.part, p.Gh * p.SD, count, even ? (const float*)ds_prev : (const float*)nullptr,
+                               even ? 1 : 0, ds_out, dz, B, p.P);
         if (even) {
             float* t = ds_prev ? ds_prev : w.dsb;
             ds_prev = ds_out;
@@ -3022,79 +2970,60 @@ int res8_bwd_impl(const HowlRes8Params* prm, const float* feat, long sb, long st
         }
         // data gradient: dx_{i-1} (w.r.t. the normalised input of layer i), with BN_{i-1} backward statistics;
         // weight gradient of layer i: input x_{i-1} = BN_{i-1}(s_{i-1}) (identity for i = 1)
-        const float* in_stats = (i == 1) ? nullptr : sv->bn_stats + (size_t)(i - 2) * 2 * CP;
         const bool need_stats = i > 1;
-        const float* wpb = w.wp_bwd + (size_t)(i - 1) * 3 * KSTEPS * 64;
+        a.s_prev = sv->s[i - 1];
+        a.in_stats = need_stats ? sv->bn_stats + (size_t)(i - 2) * 2 * CP : nullptr;
+        a.wp = w.wp_bwd + (size_t)(i - 1) * 3 * KSTEPS * 64;
+        a.dx = dx_next;
         // layer 1 needs no statistics (conv0 has no BatchNorm in front): its data gradient takes the skip gradient ds_2 as an
         // addend instead, so that dx_0 + ds_2 = the gradient of conv0's pooled output leaves the launch as ONE map
-        const float* xs = need_stats ? sv->s[i - 1] : (const float*)ds_prev;
-        const float* xs_st = need_stats ? in_stats : (const float*)nullptr;
-        float* spart = need_stats ? part_out : (float*)nullptr;
-        float* wpart = w.wpart + (size_t)(i - 1) * wpart_stride;
+        a.xs = need_stats ? sv->s[i - 1] : (const float*)ds_prev;
+        a.xs_stats = a.in_stats;
+        a.spart = need_stats ? part_out : nullptr;
+        a.wpart = w.wpart + (size_t)(i - 1) * p.wpart_stride;
         // the partials of layer i+1's weight gradient (previous launch) are folded by this launch's data-gradient workgroups
-        const WFold wf = (fold_in_pair && i < 6) ? WFold{w.wpart + (size_t)i * wpart_stride, Gh, gr->conv_w[i]} : WFold{nullptr, 0, nullptr};
+        a.wf = (p.fold_in_pair && i < 6) ? WFold{w.wpart + (size_t)i * p.wpart_stride, p.Gh, gr->conv_w[i]} : WFold{nullptr, 0, nullptr};
         if (!run_layers) {
             // part 2 only replays the buffer rotation of the loop
-        } else if (merged) {
+        } else if (p.merged) {
             HowlProfScope prof("bwd_pair", stream);
-            launch_pair(SD, SW, Gh, lp, stream, zc, bfold, wpb, dx_next, xs, xs_st, spart, sv->s[i - 1], in_stats, wpart, Bv, H, wf, halo, sp.sg);
+            launch_pair(p, stream, a);
         } else {
             {
                 HowlProfScope prof("conv3x3_dgrad", stream);
-                launch_conv3x3<1>(SD, Gh, lc, stream, zc, nullptr, wpb, nullptr, dx_next, xs, xs_st, spart, Bv, H, BnFold{}, bfold, nullptr, wf, halo, sp.sg);
+                Conv3x3Launch d;
+                d.in = a.zc, d.wp = a.wp, d.out = a.dx, d.xs = a.xs, d.xs_stats = a.xs_stats, d.part = a.spart;
+                d.bfold = a.bfold, d.wf = a.wf;
+                launch_conv3x3<1>(p, stream, d);
             }
             HowlProfScope prof("wgrad", stream);
-            StageCfg zw = zc;
-            zw.ds = nullptr;
-            if (halo == 2)
-                launch_wgrad_inst<1, 2>(Gh, lw, stream, zw, bfold, sv->s[i - 1], in_stats, wpart, Bv, H, sp.sg);
-            else if (halo == 1)
-                launch_wgrad_inst<1, 1>(Gh, lw, stream, zw, bfold, sv->s[i - 1], in_stats, wpart, Bv, H);
-            else if (SW == 2)
-                launch_wgrad_inst<2>(Gh, lw, stream, zw, bfold, sv->s[i - 1], in_stats, wpart, B, H);
-            else
-                launch_wgrad_inst<1>(Gh, lw, stream, zw, bfold, sv->s[i - 1], in_stats, wpart, B, H);
+            launch_wgrad(p, stream, a);
         }
         dx_cur = dx_next;
         dx_next = (dx_next == w.bufa) ? w.bufb : w.bufa;
     }
     // conv0: dy0 = dx_0 + ds_2 (skip into s_2 = y_2 + y_0), summed by layer 1's data gradient (ConvEpilogue::xadd)
     HOWL_REQUIRE(sv->mask0 != nullptr, "howl_res8_bwd: saved->mask0 is required");
-    HowlPtrs6 gw;
-    for (int i = 0; i < 6; ++i) gw.p[i] = gr->conv_w[i];
-    const int S0 = conv0_slices(Bv);
-    const int G0w = Bv * S0 < howl_num_cus() ? Bv * S0 : howl_num_cus();   // conv0's weight-gradient grid: one partial row each
+    const HowlPtrs6 gw = ptrs6(gr->conv_w);
     // layers 2..6 were folded inside the pair launches (WFold); layer 1's partials and conv0's remain
     const RowsAdamW no_opt{nullptr, nullptr, nullptr, nullptr, HowlAdamWCoef{}, 0, 0, 0};
+    const auto reduce_rows = [&](int cols, int first, int skip, int nrows, const RowsAdamW& opt) {
+        hipLaunchKernelGGL(reduce_rows_all_kernel, dim3((cols + 63) / 64, nrows + (opt.on ? 1 : 0)), dim3(1024), 0, stream,
+                           (const float*)w.wpart, p.wpart_stride, p.Gh, gw, (const float*)w.c0part, p.G0w, gr->conv0_w, first, skip,
+                           nrows, opt);
+    };
     if (part == 1)      // the six layers' weight gradients are final before conv0's is even started
-        hipLaunchKernelGGL(reduce_rows_all_kernel, dim3((CP * WNCOL + 63) / 64, fold_in_pair ? 1 : 6), dim3(1024), 0, stream,
-                           (const float*)w.wpart, wpart_stride, Gh, gw, (const float*)w.c0part, G0w, gr->conv0_w, 0, 0,
-                           fold_in_pair ? 1 : 6, no_opt);
+        reduce_rows(CP * WNCOL, 0, 0, p.fold_in_pair ? 1 : 6, no_opt);
     if (run_conv0) {
         {
-        HowlProfScope prof("conv0_wgrad", stream);
-        const int Tw = grid ? 3 * H : T;      // frames of one row strip (its window of the clip), or the utterance
-        const size_t l0w = ((size_t)(Tw + 2) * (M + 4) + 16) * sizeof(float);
-#define HOWL_CONV0_WGRAD(NS_, EX_)                                                                                                \
-    hipLaunchKernelGGL((conv0_wgrad_valu_kernel<NS_, EX_>), dim3(G0w), dim3(C0G_THREADS), l0w, stream, feat, sb, st, sm,           \
-                       (const unsigned short*)sv->mask0, (const float*)dx_cur, (const float*)nullptr, w.c0part, B, Tw, M, H, S0,  \
-                       sp.sg, T)
-        if (grid && NS == 2)
-            HOWL_CONV0_WGRAD(2, true);
-        else if (grid)
-            HOWL_CONV0_WGRAD(1, true);
-        else if (NS == 2)
-            HOWL_CONV0_WGRAD(2, false);
-        else
-            HOWL_CONV0_WGRAD(1, false);
-#undef HOWL_CONV0_WGRAD
+            HowlProfScope prof("conv0_wgrad", stream);
+            launch_conv0_wgrad(p, stream, feat, sv->mask0, dx_cur);
         }
         if (part == 0) {    // rows {layer 1, conv0} of the reduction (small batches: all six layers and conv0)
             // ... and, on a single replica, the optimiser step (HowlAdamW): folded rows are updated as they are written, one more
             // row of blocks takes the parameters whose gradients were final before this launch.  Only for gradient pointers
             // that ARE the flat buffer in hot_parameters() order (conv0, conv1..6, output.weight, output.bias); otherwise the
             // step runs as its own launch behind this one.
-            const int nrows = fold_in_pair ? 2 : 7;
             RowsAdamW opt = no_opt;
             bool own_launch = adamw != nullptr;
             if (adamw != nullptr && getenv("HOWL_NO_FOLD_ADAMW") == nullptr) {
@@ -3104,26 +3033,21 @@ int res8_bwd_impl(const HowlRes8Params* prm, const float* feat, long sb, long st
                             gr->out_w == g0 + (size_t)NMAP * 9 + (size_t)6 * NMAP * NMAP * 9;
                 for (int i = 0; i < 6; ++i) flat = flat && gr->conv_w[i] == g0 + (size_t)NMAP * 9 + (size_t)i * NMAP * NMAP * 9;
                 if (flat) {
-                    const double bc1 = 1.0 - pow((double)adamw->beta1, (double)adamw->step);
-                    const double bc2 = 1.0 - pow((double)adamw->beta2, (double)adamw->step);
                     opt = RowsAdamW{adamw->p, g0, adamw->m, adamw->v,
-                                    HowlAdamWCoef{adamw->lr, adamw->beta1, adamw->beta2, adamw->eps, adamw->weight_decay, (float)bc1,
-                                                  (float)sqrt(bc2), adamw->grad_scale},
-                                    (long)((fold_in_pair ? gr->conv_w[1] : gr->out_w) - g0), (long)adamw->n, 1};
+                                    howl_adamw_coef(adamw->lr, adamw->beta1, adamw->beta2, adamw->eps, adamw->weight_decay, adamw->step,
+                                                    adamw->grad_scale),
+                                    (long)((p.fold_in_pair ? gr->conv_w[1] : gr->out_w) - g0), (long)adamw->n, 1};
                     own_launch = false;
                 }
             }
-            hipLaunchKernelGGL(reduce_rows_all_kernel, dim3((CP * WNCOL + 63) / 64, nrows + (opt.on ? 1 : 0)), dim3(1024), 0, stream,
-                               (const float*)w.wpart, wpart_stride, Gh, gw, (const float*)w.c0part, G0w, gr->conv0_w, 0,
-                               fold_in_pair ? 5 : 0, nrows, opt);
+            reduce_rows(CP * WNCOL, 0, p.fold_in_pair ? 5 : 0, p.fold_in_pair ? 2 : 7, opt);
             if (own_launch) {
                 const int rc = howl_adamw_step(adamw->p, adamw->g, adamw->m, adamw->v, adamw->n, adamw->lr, adamw->beta1, adamw->beta2,
                                                adamw->eps, adamw->weight_decay, adamw->step, adamw->grad_scale, stream);
                 if (rc != HOWL_OK) return rc;
             }
         } else {
-            hipLaunchKernelGGL(reduce_rows_all_kernel, dim3((NMAP * 9 + 63) / 64, 1), dim3(1024), 0, stream,
-                               (const float*)w.wpart, wpart_stride, Gh, gw, (const float*)w.c0part, G0w, gr->conv0_w, 6, 0, 1, no_opt);
+            reduce_rows(NMAP * 9, 6, 0, 1, no_opt);
         }
     }
     HOWL_CHECK_LAUNCH("howl_res8_bwd");
@@ -3134,23 +3058,97 @@ int res8_bwd_impl(const HowlRes8Params* prm, const float* feat, long sb, long st
 
 extern "C" {
 
-int howl_res8_bwd_part(const HowlRes8Params* prm, const float* feat, long sb, long st, long sm, int B, int T, int M, int C,
-                       const HowlRes8Saved* sv, const float* dlogits, const HowlRes8Grads* gr, void* ws, size_t ws_bytes,
-                       int part, hipStream_t stream) {
-    return res8_bwd_impl(prm, feat, sb, st, sm, B, T, M, C, sv, dlogits, gr, ws, ws_bytes, part, nullptr, nullptr, stream);
+size_t howl_res8_workspace_bytes(int B, int T) { return res8_plan(B, T, 40).train_bytes; }
+size_t howl_res8_workspace_bytes_mels(int B, int T, int M) { return res8_plan(B, T, M).train_bytes; }
+size_t howl_res8_saved_floats(int B, int T, int M) { return res8_plan(B, T, M).saved_floats; }
+size_t howl_res8_eval_workspace_bytes_mels(int B, int T, int M) { return res8_plan(B, T, M).eval_bytes; }
+int howl_res8_row_strips(int T) { return res8_plan(1, T, 40).nr; }
+
+int howl_res8_fwd(const HowlRes8Params* prm, const float* feat, long sb, long st, long sm, int B, int T, int M, int C,
+                  int training, const HowlRes8Saved* sv, float* logits, void* ws, size_t ws_bytes, hipStream_t stream) {
+    return res8_fwd_impl(prm, Feat{feat, sb, st, sm}, B, T, M, C, training, sv, logits, ws, ws_bytes, nullptr, nullptr, nullptr, stream);
+}
+
+size_t howl_res8_long_workspace_bytes(int B, int T) { return res8_long_plan(B, T, 40).long_bytes; }
+size_t howl_res8_long_workspace_bytes_mels(int B, int T, int M) { return res8_long_plan(B, T, M).long_bytes; }
+
+// the windows (see WIN_H) run as a virtual batch through the eval-mode layers; only the head sees them together
+int howl_res8_fwd_long(const HowlRes8Params* prm, const float* feat, long sb, long st, long sm, int B, int T, int M, int C,
+                       float* logits, void* ws, size_t ws_bytes, hipStream_t stream) {
+    HOWL_REQUIRE(prm && feat && logits && ws, "howl_res8_fwd_long: null pointer");
+    HOWL_REQUIRE(mel_strips(M) > 0, "howl_res8_fwd_long: res8 pools (3,4) over 40 or 80 mel bins; got M=%d", M);
+    const int H = T / 3;
+    HOWL_REQUIRE(B >= 1 && H > WIN_H && C >= 1, "howl_res8_fwd_long: for T > 83 frames (got B=%d T=%d); shorter inputs use howl_res8_fwd", B, T);
+    const int nw = long_windows(H);
+    HOWL_REQUIRE(nw <= MAX_WINDOWS, "howl_res8_fwd_long: T=%d needs %d windows (max %d)", T, nw, MAX_WINDOWS);
+    const Res8Plan p = res8_long_plan(B, T, M, ws);
+    if (int rc = check_workspace("howl_res8_fwd_long", ws_bytes, p.long_bytes)) return rc;
+    char* base = static_cast<char*>(ws);
+    float* buf[3];
+    for (int i = 0; i < 3; ++i) buf[i] = reinterpret_cast<float*>(base + i * p.long_map_bytes);
+    float* stats = reinterpret_cast<float*>(base + 3 * p.long_map_bytes);
+    HowlWinRows rows;
+    for (int i = 0; i < nw; ++i) {
+        const int a = i * WIN_STEP < H - WIN_H ? i * WIN_STEP : H - WIN_H;          // first pooled row of window i
+        const int a_next = (i + 1) * WIN_STEP < H - WIN_H ? (i + 1) * WIN_STEP : H - WIN_H;
+        const int g_lo = i == 0 ? 0 : a + WIN_MARGIN;                              // clip rows [g_lo, g_hi) come from window i
+        const int g_hi = i == nw - 1 ? H : a_next + WIN_MARGIN;
+        rows.lo[i] = g_lo - a;
+        rows.hi[i] = g_hi - a;
+    }
+    hipLaunchKernelGGL(bn_eval_stats_kernel, dim3(6), dim3(64), 0, stream, ptrs6(prm->bn_running_mean), ptrs6(prm->bn_running_var), stats);
+    launch_conv0_fwd(p, stream, Feat{feat, sb, st, sm}, prm, buf[0], nullptr);
+    // x_i lives in buf[cur]; even layers add the map two layers back (kept in buf[skip])
+    int cur = 0, skip = 0;
+    for (int i = 1; i <= 6; ++i) {
+        const bool even = (i % 2) == 0;
+        int out = 0;
+        while (out == cur || out == skip) ++out;
+        Conv3x3Launch a;
+        a.in = plain_tile(buf[cur]);
+        a.in_stats = i == 1 ? nullptr : stats + (size_t)(i - 2) * 2 * CP;
+        a.wp = p.ws.wp_fwd + (size_t)(i - 1) * 3 * KSTEPS * 64;
+        a.res = even ? buf[skip] : nullptr;
+        a.out = buf[out];
+        launch_conv3x3<0>(p, stream, a);
+        if (even) skip = out;      // s_i (i even) is the next residual source; s_0 is the first one
+        cur = out;
+    }
+    hipLaunchKernelGGL(head_fwd_windows_kernel, dim3(B < 1024 ? B : 1024), dim3(256), 0, stream, (const float*)buf[cur],
+                       (const float*)(stats + (size_t)5 * 2 * CP), prm->out_w, prm->out_b, logits, B, nw, WIN_H, rows,
+                       1.0f / ((float)H * PW * p.ns), C, p.ns);
+    HOWL_CHECK_LAUNCH("howl_res8_fwd_long");
+    return HOWL_OK;
 }
 
 int howl_res8_bwd(const HowlRes8Params* prm, const float* feat, long sb, long st, long sm, int B, int T, int M, int C,
                   const HowlRes8Saved* sv, const float* dlogits, const HowlRes8Grads* gr, void* ws, size_t ws_bytes,
                   hipStream_t stream) {
-    return res8_bwd_impl(prm, feat, sb, st, sm, B, T, M, C, sv, dlogits, gr, ws, ws_bytes, 0, nullptr, nullptr, stream);
+    return res8_bwd_impl(prm, Feat{feat, sb, st, sm}, B, T, M, C, sv, dlogits, gr, ws, ws_bytes, 0, nullptr, nullptr, stream);
+}
+
+// part 0: the whole backward pass.  Data-parallel steps call it in two parts so that the gradient all-reduce of everything
+// but conv0 runs under conv0's weight gradient: part 1 = head + layers 6..1 (data and weight gradients) + the fold of the six
+// layers' weight-gradient partials -- after it gr->conv_w[0..5], gr->out_w, gr->out_b are final; part 2 = conv0's weight
+// gradient and its fold (gr->conv0_w).  The two parts of a pass must be called in order with identical arguments.
+int howl_res8_bwd_part(const HowlRes8Params* prm, const float* feat, long sb, long st, long sm, int B, int T, int M, int C,
+                       const HowlRes8Saved* sv, const float* dlogits, const HowlRes8Grads* gr, void* ws, size_t ws_bytes,
+                       int part, hipStream_t stream) {
+    return res8_bwd_impl(prm, Feat{feat, sb, st, sm}, B, T, M, C, sv, dlogits, gr, ws, ws_bytes, part, nullptr, nullptr, stream);
+}
+
+int howl_res8_fwd_xent(const HowlRes8Params* prm, const float* feat, long sb, long st, long sm, int B, int T, int M, int C,
+                       const HowlRes8Saved* sv, const long long* labels, float* logits, float* nll, float* dlogits, void* ws,
+                       size_t ws_bytes, hipStream_t stream) {
+    HOWL_REQUIRE(labels && nll && dlogits, "howl_res8_fwd_xent: null pointer");
+    return res8_fwd_impl(prm, Feat{feat, sb, st, sm}, B, T, M, C, 1, sv, logits, ws, ws_bytes, labels, nll, dlogits, stream);
 }
 
 int howl_res8_bwd_xent(const HowlRes8Params* prm, const float* feat, long sb, long st, long sm, int B, int T, int M, int C,
                        const HowlRes8Saved* sv, const float* dlogits, const float* nll, float* loss, const HowlRes8Grads* gr,
                        void* ws, size_t ws_bytes, int part, const HowlAdamW* adamw, hipStream_t stream) {
     HOWL_REQUIRE(nll && loss, "howl_res8_bwd_xent: null pointer");
-    return res8_bwd_impl(prm, feat, sb, st, sm, B, T, M, C, sv, dlogits, gr, ws, ws_bytes, part, nll, loss, stream, adamw);
+    return res8_bwd_impl(prm, Feat{feat, sb, st, sm}, B, T, M, C, sv, dlogits, gr, ws, ws_bytes, part, nll, loss, stream, adamw);
 }
 
 int howl_xent_fwd_bwd(const float* logits, const long long* labels, int B, int C, float* loss, float* dlogits,
@@ -3167,12 +3165,10 @@ int howl_adamw_step(float* p, const float* g, float* m, float* v, size_t n, floa
     HOWL_REQUIRE(p && g && m && v, "howl_adamw_step: null pointer");
     HOWL_REQUIRE(step >= 1, "howl_adamw_step: step counts from 1");
     if (n == 0) return HOWL_OK;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
     size_t blocks = (n + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, n,
-                       HowlAdamWCoef{lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale});
+                       howl_adamw_coef(lr, beta1, beta2, eps, weight_decay, step, grad_scale));
     HOWL_CHECK_LAUNCH("howl_adamw_step");
     return HOWL_OK;
 }

@@ -31,6 +31,17 @@ def _vp(t):
     return t.data_ptr()
 
 
+def _saved_struct(s, buf):
+    """``HowlRes8Saved`` over the seven activation tensors ``s`` and ``buf``'s statistics, pooled means and conv0 mask."""
+    saved = _lib.HowlRes8Saved()
+    for i in range(7):
+        saved.s[i] = _vp(s[i])
+    saved.bn_stats = _vp(buf.bn_stats)
+    saved.pooled = _vp(buf.pooled)
+    saved.mask0 = _vp(buf.mask0)
+    return saved
+
+
 class _Res8Buffers:
     """Caller-owned activations / workspace for one (B, T, M) geometry, reused across steps.  The activations are the
     library's: (B, 45, T/3, M/4) floats each, in the reference's NCHW order at 40 mel bins and as two 10-column strips per
@@ -47,12 +58,7 @@ class _Res8Buffers:
         self.mask0 = torch.empty(n, dtype=torch.int16, device=device)
         nbytes = _lib.get().cdll.howl_res8_workspace_bytes_mels(B, T, M)
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        self.saved = _lib.HowlRes8Saved()
-        for i in range(7):
-            self.saved.s[i] = _vp(self.s[i])
-        self.saved.bn_stats = _vp(self.bn_stats)
-        self.saved.pooled = _vp(self.pooled)
-        self.saved.mask0 = _vp(self.mask0)
+        self.saved = _saved_struct(self.s, self)
 
 
 class _Res8EvalBuffers:
@@ -67,12 +73,7 @@ class _Res8EvalBuffers:
         self.pooled = torch.empty((B, 48), **f32)
         self.mask0 = torch.empty(n, dtype=torch.int16, device=device)
         self.ws = torch.empty(_lib.get().cdll.howl_res8_eval_workspace_bytes_mels(B, T, M), dtype=torch.uint8, device=device)
-        self.saved = _lib.HowlRes8Saved()
-        for i in range(7):
-            self.saved.s[i] = _vp(self.rot[i % 3])
-        self.saved.bn_stats = _vp(self.bn_stats)
-        self.saved.pooled = _vp(self.pooled)
-        self.saved.mask0 = _vp(self.mask0)
+        self.saved = _saved_struct([self.rot[i % 3] for i in range(7)], self)
 
 
 class _Res8Function(torch.autograd.Function):
@@ -493,22 +494,6 @@ class MobileNetClassifier(RegisteredModel, name="mobilenet"):
             ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
         self._ws_cache[key] = ws
         return ws
-
-    EVAL_CACHE_BYTES = 256 << 20     # eval buffers kept between calls (streaming engines re-use one small geometry)
-
-    def _get_eval_buffers(self, B, T, device, M=40):
-        """Eval-mode buffers: cached while small (an engine's (1, 51..83)-frame windows), transient beyond -- an evaluation pass
-        batches the windows of many clips (``infer_many``) with a different B per call, and a long clip's strips are large."""
-        key = (B, T, M, self.num_labels, str(device))
-        buf = self._eval_cache.pop(key, None)
-        if buf is None:
-            buf = _Res8EvalBuffers(B, T, self.num_labels, device, M)
-        size = lambda b: b.ws.numel() + 4 * 3 * b.rot[0].numel() + 2 * b.mask0.numel()
-        if size(buf) <= self.EVAL_CACHE_BYTES // 4:
-            self._eval_cache[key] = buf
-            while sum(size(b) for b in self._eval_cache.values()) > self.EVAL_CACHE_BYTES:
-                self._eval_cache.pop(next(iter(self._eval_cache)))
-        return buf
 
     @staticmethod
     def _feat_view(x):

@@ -1,3 +1,5 @@
+# NOTE: the host side of csrc/res8.hip was reorganised around Res8Plan and the probe hooks removed; the literal lines this tool substitutes are gone;
+# it builds against the sources of commit cd250aa (`git worktree add /tmp/howl_r6 cd250aa` and run it there).
 """Round-6 A/B harness: libraries built from EDITED copies of csrc/res8.hip (text substitutions; tools only, nothing here ships,
 most variants compute WRONG results by design: they time a kernel with one part removed) and the c1 / c2 step timed with each on
 one GPU box, same minute.  The product sources carry no ablation branches; the edits live here.
