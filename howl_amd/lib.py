@@ -150,6 +150,15 @@ SIZE_FUNCS = {"howl_fb_packed_floats": [c_int], "howl_res8_workspace_bytes": [c_
               "howl_ctc_supported": [c_int, c_int, c_int], "howl_ctc_workspace_floats": [c_int, c_int]}
 
 
+# The streaming res8 entry points of ``include/howl_hip_stream.h`` (a table of their own: ``tests/test_emu_res8_stream.py`` checks it
+# against that header the way ``tests/test_cabi.py`` checks the tables above against ``howl_hip.h``)
+STREAM_SIGNATURES = {
+    "howl_res8_stream_prepare": [POINTER(HowlRes8Params), c_int, P, c_size_t, STREAM],
+    "howl_res8_stream_windows": [P, P, c_long, c_int, c_int, P, c_int, c_float, P, c_int, P, P, STREAM],
+}
+STREAM_SIZE_FUNCS = {"howl_res8_stream_supported": [c_int, c_int, c_int], "howl_res8_stream_state_bytes": [c_int]}
+
+
 class HowlHipError(RuntimeError):
     pass
 
@@ -165,11 +174,11 @@ class Library:
         self.cdll = ctypes.CDLL(str(path))
         self.cdll.howl_last_error.restype = c_char_p
         self.cdll.howl_last_error.argtypes = []
-        for name, argtypes in SIGNATURES.items():
+        for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES}.items():
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = c_int
             fn.argtypes = argtypes
-        for name, argtypes in SIZE_FUNCS.items():
+        for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS}.items():
             fn = getattr(self.cdll, name)
             fn.restype = c_size_t
             fn.argtypes = argtypes

@@ -6,6 +6,7 @@ model (instead of one launch and one device->host sync per 63 ms stride, ``infer
 the reference's per-window loop on the host, so ``label_history`` / ``pred_history`` and the early exit are identical.
 Models that carry streaming state between windows keep the sequential path.
 """
+import os
 import time
 
 import numpy as np
@@ -19,6 +20,7 @@ from howl_amd.settings import SETTINGS
 from howl_amd.utils import audio_utils
 
 from .base import RegisteredModel
+from .cnn import Res8
 from .decision import ProbabilitySmoother, SequenceMatcher
 
 __all__ = ["FrameInferenceEngine", "InferenceEngine"]
@@ -128,6 +130,9 @@ class FrameInferenceEngine(InferenceEngine):
     def __init__(self, max_window_size_ms: int, eval_stride_size_ms: int, *args):
         super().__init__(*args)
         self.max_window_size_ms, self.eval_stride_size_ms = max_window_size_ms, eval_stride_size_ms
+        # ingest_frame as ONE launch (Res8StreamSession) instead of the frontend + res8 + softmax chain: off unless asked for
+        self.fused_windows = os.environ.get("HOWL_STREAM_FUSED") == "1"
+        self._stream_session = None
 
     def _stateless(self) -> bool:
         return not self.model.is_streaming or type(self.model).streaming_state is RegisteredModel.streaming_state
@@ -249,10 +254,24 @@ class FrameInferenceEngine(InferenceEngine):
                 break
         return sequence_present
 
+    def _fused_session(self, frame):
+        """The streaming session for this window, or None when it does not apply (another model, training mode, a window outside
+        the kernel's range): ``ingest_frame`` then takes the launch chain."""
+        if not isinstance(self.model, Res8) or self.model.training or frame.dim() != 1 or frame.dtype != torch.float32:
+            return None
+        s = self._stream_session
+        if s is None or s.model is not self.model or s.std is not self.std or s.zmuv is not self.zmuv:
+            s = self._stream_session = self.model.stream_session(self.std, self.zmuv)
+        return s if s.supported(frame.size(-1)) else None
+
     @torch.no_grad()
     def ingest_frame(self, frame: torch.Tensor, curr_time: float = None) -> int:
         """One window, as the live client feeds it (``inference.py:247-267``)."""
         self.std = self.std.to(frame.device)
+        session = self._fused_session(frame) if self.fused_windows else None
+        if session is not None:      # one launch, one host copy
+            prediction = session.probabilities(frame.reshape(1, -1))[0].cpu().numpy()
+            return self._append_probability_frame(self._weighted(prediction), curr_time=curr_time)
         lengths = torch.tensor([frame.size(-1)]).to(frame.device)
         transformed_lengths = self.std.compute_lengths(lengths)
         transformed_frame = self.std.log_mel_for_model(frame.unsqueeze(0), self.zmuv)

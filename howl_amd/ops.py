@@ -259,3 +259,37 @@ def ctc_loss(scores, targets, input_lengths, target_lengths, blank: int):
 def adamw_step(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=1.0):
     _lib.get().call("howl_adamw_step", _p(p), _p(g), _p(m), _p(v), p.numel(), lr, betas[0], betas[1], eps,
                     weight_decay, step, grad_scale, _stream())
+
+
+# ---- streaming res8 (include/howl_hip_stream.h): one launch from the windows' PCM to their probabilities ----------------------------
+
+def res8_stream_supported(n_samples: int, n_mels: int, n_labels: int) -> bool:
+    return bool(_lib.get().cdll.howl_res8_stream_supported(int(n_samples), int(n_mels), int(n_labels)))
+
+
+def res8_stream_state_bytes(n_labels: int) -> int:
+    return int(_lib.get().cdll.howl_res8_stream_state_bytes(int(n_labels)))
+
+
+def res8_stream_prepare(prm, n_labels: int, state: torch.Tensor) -> torch.Tensor:
+    """``prm``: a ``HowlRes8Params`` record (``Res8._params_struct``) -> the prepared ``state`` (uint8, ``res8_stream_state_bytes``)."""
+    _lib.get().call("howl_res8_stream_prepare", ctypes.byref(prm), int(n_labels), _p(state, torch.uint8), state.numel(), _stream())
+    return state
+
+
+def res8_stream_windows(state, pcm, fbp, n_mels, zmuv_pair, n_labels, probs=None, logits=None, log_eps: float = 1e-7):
+    """(N, L) PCM windows (unit sample stride, any row stride: overlapping views of one clip are fine) -> (N, C) probabilities in one
+    launch; ``logits`` (N, C), when given, receives the pre-softmax scores."""
+    if pcm.dim() != 2:
+        raise ValueError("pcm must be (N, L)")
+    if pcm.stride(1) != 1:
+        pcm = pcm.contiguous()
+    if not on_device(pcm) or pcm.dtype != torch.float32:
+        _p(pcm)
+    N, L = pcm.shape
+    if probs is None:
+        probs = torch.empty((N, n_labels), dtype=torch.float32, device=pcm.device)
+    _lib.get().call("howl_res8_stream_windows", _p(state, torch.uint8), ctypes.c_void_p(pcm.data_ptr()), pcm.stride(0), N, L, _p(fbp),
+                    int(n_mels), log_eps, _p(zmuv_pair, allow_none=True), int(n_labels), _p(probs), _p(logits, allow_none=True),
+                    _stream())
+    return probs

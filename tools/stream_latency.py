@@ -1,0 +1,114 @@
+"""Latency of the live client's window, eager launch chain against the one-launch streaming kernel (Res8StreamSession).
+
+Protocol: wall time per window of ``FrameInferenceEngine.ingest_frame``, from the call to the label, host copy included; 500 ms
+windows at a 63 ms stride over the 10 s synthetic clips that ``bench.py --config eval`` uses; 200 windows of warm-up per path, then
+five repeats of 1000 windows each, the MEDIAN of each repeat; eager (``fused_windows = False``) and fused alternate repeat by repeat,
+in one process, on one card.  In addition, for N = 64 and N = 256 windows per launch: ``Res8StreamSession.probabilities`` alone
+between two HIP events beside ``engine.window_probabilities`` on the same windows (wall time, host copy included: what that call
+is).  Prints one JSON line.  ``--windows`` / ``--repeats`` shorten a run (a profiler pass); the protocol is the default."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+if str(ROOT) not in sys.path:
+    sys.path.insert(0, str(ROOT))
+os.environ.setdefault("NUM_MELS", "40")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", type=int, default=1000)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--fused-only", action="store_true", help="skip the eager path (a kernel-trace pass over the one launch)")
+    args = ap.parse_args()
+    import torch
+    from howl_amd.context import InferenceContext
+    from howl_amd.data.transform.operator import ZmuvTransform
+    from howl_amd.data.transform.transform import StandardAudioTransform
+    from howl_amd.model import RegisteredModel
+    from howl_amd.model.inference import FrameInferenceEngine
+    from howl_amd.utils import audio_utils
+    from howl_amd.utils.synth import res8_closed_form_state, synthetic_pcm
+    dev = torch.device("cuda:0")
+    ctx = InferenceContext(["hey", "fire", "fox"], token_type="word", use_blank=False)
+    model = RegisteredModel.find_registered_class("res8")(ctx.num_labels).to(dev)
+    model.load_state_dict(res8_closed_form_state(ctx.num_labels), strict=False)
+    model.eval()
+    std = StandardAudioTransform().to(dev).eval()
+    zmuv = ZmuvTransform().to(dev)
+    clips = synthetic_pcm(8, 160000, seed=77).to(dev)                  # 8 clips of 10 s
+    zmuv.update(std(clips[:1, :16000]))
+    engine = FrameInferenceEngine(500, 63, model, zmuv, ctx)
+    starts, chunk = audio_utils.stride_starts(160000, 500, 63, 16000)
+    frames = [clip[s:s + chunk] for clip in clips for s in starts]     # views: 8 x 151 windows, walked round-robin
+
+    def run(fused, n, first):
+        engine.fused_windows = fused
+        engine.reset()
+        times = []
+        for i in range(n):
+            frame = frames[(first + i) % len(frames)]
+            t0 = time.perf_counter()
+            engine.ingest_frame(frame, curr_time=63.0 * i)
+            times.append(time.perf_counter() - t0)
+        return times
+
+    paths = [True] if args.fused_only else [False, True]
+    for fused in paths:
+        run(fused, args.warmup, 0)
+    medians = {True: [], False: []}
+    for r in range(args.repeats):
+        for fused in paths:
+            medians[fused].append(statistics.median(run(fused, args.windows, r * args.windows)) * 1e6)
+
+    many = []
+    session = model.stream_session(std, zmuv)
+    for n in (64, 256):
+        stride = (160000 - chunk) // n // 2 * 2
+        clip = clips[0, :chunk + (n - 1) * stride].contiguous()
+        windows = clip.as_strided((n, chunk), (stride, 1))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        fused_us = []
+        for i in range(60):
+            e0.record()
+            session.probabilities(windows)
+            e1.record()
+            e1.synchronize()
+            fused_us.append(e0.elapsed_time(e1) * 1e3)
+        row = {"windows_per_launch": n, "fused_launch_us_median": round(statistics.median(fused_us[10:]), 2)}
+        if not args.fused_only:
+            eng = FrameInferenceEngine(500, 1000.0 * stride / 16000 + 1e-6, model, zmuv, ctx)
+            assert audio_utils.stride_starts(clip.numel(), 500, eng.eval_stride_size_ms, 16000)[0] == [stride * k for k in range(n)]
+            eager_us = []
+            for i in range(60):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                eng.window_probabilities(clip)
+                eager_us.append((time.perf_counter() - t0) * 1e6)
+            t_f = []
+            for i in range(60):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                session.probabilities(windows).cpu()
+                t_f.append((time.perf_counter() - t0) * 1e6)
+            row["fused_call_and_host_copy_us_median"] = round(statistics.median(t_f[10:]), 2)
+            row["eager_window_probabilities_us_median"] = round(statistics.median(eager_us[10:]), 2)
+        many.append(row)
+    torch.cuda.synchronize()
+    fused_m, eager_m = medians[True], medians[False]
+    print(json.dumps({
+        "metric": "ingest_frame wall time per window, us (500 ms windows, 63 ms stride, 10 s synthetic clips; median of each repeat)",
+        "windows_per_repeat": args.windows, "warmup_windows": args.warmup,
+        "fused_us_medians": [round(v, 2) for v in fused_m], "eager_us_medians": [round(v, 2) for v in eager_m],
+        "requirement_max_fused_below_min_eager": (max(fused_m) < min(eager_m)) if eager_m else None,
+        "many_windows": many}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
