@@ -20,12 +20,14 @@
 //     stem convolutions (1->3, 3->32) are direct, one thread per pixel;
 //   * the layer table is built once on the host and published through howl_mobilenet_layer(): the Python module lays
 //     its parameters out in ONE flat buffer at those offsets, in PyTorch's own shapes, so gradients land in a flat
-//     buffer of the same layout and the optimiser is a single fused AdamW launch.
+//     buffer of the same layout and the optimiser is a single fused AdamW launch;
+//   * how one problem (B, M, T, num_labels) runs is decided in ONE place on the host: mb_plan builds, once per call, every
+//     layer's geometry, workspace offsets, operands and launch shapes, and says why a problem is refused; the size query,
+//     the forward and the backward read the same fields (a layer's slab area and the blocks that write it are one number),
+//     and each templated kernel has one launcher that names its instances.
 // Saved for the backward pass (in the caller's workspace): each layer's convolution output z_k, ss_k, the stored y_k of the
 // linear bottlenecks; masks and normalised values are recomputed from z_k.  Reductions are fixed-order: results do not
 // depend on scheduling.
-#include <stdlib.h>
-
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -119,7 +121,7 @@ const Net& net() {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// geometry and workspace plan for one (B, H0, W0)
+// the plan: how one problem (B, H0, W0, num_labels) runs -- geometry, workspace layout, operands and launch shapes
 // ---------------------------------------------------------------------------------------------------------
 struct Geo {
     int hin, win, ho, wo;  // convolution input / output extent
@@ -133,7 +135,8 @@ constexpr int MB_R = MB_G * MB_R2;
 constexpr int MB_MAXC = 1280;     // widest layer
 constexpr int MB_CBLOCKS = 64;    // channel blocks of a launch: 64 wide (<= 20) or 32 wide (<= 40)
 constexpr int MB_COUNTERS = MB_CBLOCKS * (MB_R2 + 1);   // arrival counters: per channel block, one per group + one for the groups
-constexpr int MB_MAX_JOBS = 60;   // deferred slab sums of one backward call (53 convolution weights)
+constexpr int MB_MAX_JOBS = 60;   // deferred slab sums of one backward call (53 convolution weights + the downsample bias)
+constexpr int MB_MAX_LAYERS = 64; // EvalJobs' arrays
 constexpr int DW_SEG = 4;
 
 // y_k exists in memory only where something other than one convolution reads it: the linear bottleneck outputs (narrow;
@@ -141,16 +144,42 @@ constexpr int DW_SEG = 4;
 // consumer while it loads z_k.
 inline bool materialized(const HowlMbLayer& l) { return l.act == MB_ACT_NONE; }
 
-struct Plan {
-    std::vector<Geo> g;
-    std::vector<size_t> z, y, gr, ss, bc, slab;  // float offsets (y: 0 when not materialised)
-    std::vector<int> nslab;                          // slabs of the layer's weight gradient
-    size_t dz = 0, slab0b = 0, part = 0, part2 = 0, counters = 0, head_scratch = 0, bias_scratch = 0, pooled = 0,
-           pooled_d = 0;
-    size_t total_floats = 0;
+// Layer k of a plan.  Offsets count floats from the start of the workspace; -1: no such operand.
+struct MbLayer {
+    const HowlMbLayer* l;
+    Geo g;
+    long z, gr, y, ss, bc, slab;      // (y: -1 unless materialised)
+    int nslab;      // slabs of the weight gradient: sizes `slab` AND is the backward launch's w_nz / w_chunks / stem blocks
+    // The layer's input as the backward launch and a depthwise forward read it (b_in, b_ss): y_{k-1} where it exists, else
+    // z_{k-1} with the BatchNorm + ReLU6 of layer k-1 applied on load.  A pointwise forward always reads z_{k-1} with ss_{k-1}
+    // (f_in, f_ss): behind a materialised layer it builds y_{k-1} = bn(z_{k-1}) (+ f_res) on load and stores it for the later
+    // readers (f_yout).  addend: g of the later layer whose output adds y_k (y = bn(z) + y_k, no activation: dy = g).
+    long f_in = -1, f_ss = -1, f_res = -1, f_yout = -1, b_in = -1, b_ss = -1, addend = -1;
+    // forward launch: f_cx channel blocks x f_ry row blocks.  Pointwise: f_tile x f_tile tiles, f_per row tiles per block;
+    // depthwise / stem0 / col_stats (features[0]): f_per image rows / pixels / pixel rows per block, cp = col_pack
+    int f_tile, f_cx, f_ry, f_per, cp;
+    // backward launch, pointwise (PwBwd): d_tile x 64 data-gradient tiles, then the weight-gradient blocks
+    int d_tile, tiles_per_block, d_cx, d_ry, rows_per_split, w_cx, w_ny;
+    // depthwise (DwBwd; w_rows = B * ho is also what the forward walks)
+    int ncb, d_rows, d_rpc, d_chunks, w_rows, w_rpc;
+    // stem (stem0_bwd_kernel, Stem1Bwd)
+    int px_per_block, cls_blocks, px_per_thread;
 };
 
-// row tiles of a pointwise launch: each block takes a run of consecutive 64-row tiles
+// Built once per call by mb_plan and by nobody else: the size query, the forward and the backward read the same fields.
+struct MbPlan {
+    const char* bad = nullptr;      // why this problem is refused, or nullptr
+    int B = 0;
+    float* ws = nullptr;            // the caller's workspace (null in a size query)
+    std::vector<MbLayer> L;
+    long dz = 0, slab0b = 0, part = 0, part2 = 0, counters = 0, head_scratch = 0, bias_scratch = 0, pooled = 0, pooled_d = 0;
+    int pool_chunks = 0, pool_upc = 0;      // avgpool_bwd_reduce_kernel: chunks of utterances
+    size_t total_floats = 0;
+    size_t bytes() const { return total_floats == 0 ? 0 : total_floats * sizeof(float) + 256; }      // (0: bad shape)
+    float* at(long off) const { return off < 0 ? nullptr : ws + off; }
+};
+
+// row tiles of a pointwise launch: each block takes a run of consecutive `tile`-row tiles
 inline void pw_rows(long M, int col_tiles, int* tiles_per_block, int* blocks, int tile = 64) {
     const int row_tiles = (int)((M + tile - 1) / tile);
     int tpb = (int)(((long)row_tiles * col_tiles + 4095) / 4096);     // ~4096 blocks at most ...
@@ -159,16 +188,11 @@ inline void pw_rows(long M, int col_tiles, int* tiles_per_block, int* blocks, in
     *tiles_per_block = tpb;
     *blocks = (row_tiles + tpb - 1) / tpb;
 }
-// tile edge of a pointwise product with an (M x n) result: 32 when 64 x 64 tiles would not give every CU a block
-inline int env_int(const char* name, int fallback) {
-    const char* v = getenv(name);
-    return v != nullptr && v[0] != 0 ? atoi(v) : fallback;
-}
-inline int pw_tile(long M, int n) {
-    const long tiles64 = ((M + 63) / 64) * ((n + 63) / 64);
-    static const int per_cu = env_int("HOWL_MB_TILE_BLOCKS_PER_CU", 1);    // fewer 64 x 64 tiles than this per CU -> 32-row tiles
-    return tiles64 < (long)per_cu * howl_num_cus() ? 32 : 64;
-}
+// Rows of a tile of a pointwise product with an (M x n) result: 32 when 64 x 64 tiles would not give every CU a block (the
+// late, deep-reduction bottleneck layers: 96-192 tiles) -- the forward then takes 32 x 32 tiles (four times the blocks, a
+// quarter of the MFMA chain per step), the data gradient 32 x 64.  DESIGN.md 5c has the sweep that chose this rule and its
+// losers (32 x 64 forward, 32 x 32 data gradient, 32-row tiles up to 2 / 4 / 8 tiles per CU).
+inline int pw_tile(long M, int n, int cus) { return ((M + 63) / 64) * ((n + 63) / 64) < cus ? 32 : 64; }
 // The weight-gradient blocks of a pointwise backward launch run beside its data-gradient blocks: a split is sized so that both
 // kinds take about the same number of 64-deep steps (data gradient: tiles_per_block x ceil(N / 64)), which keeps the slabs
 // that the deferred sum has to read few.
@@ -186,11 +210,8 @@ inline int stem_px_per_block(long pixels) {
     per = (per + 255) / 256 * 256;
     return (int)(per < 256 ? 256 : per);
 }
-inline int stem_blocks(long pixels) {
-    const long per = stem_px_per_block(pixels);
-    return (int)((pixels + per - 1) / per);
-}
-// chunks of image rows for the depthwise kernels / pixel rows for the narrow column reductions: >= `min_per` units each
+// chunks of image rows for the depthwise kernels / pixel rows for the narrow column reductions: >= `min_per` units each, at
+// most MB_R chunks
 inline int row_chunks(long units, int min_per, int* per_chunk) {
     long c = units / min_per;
     c = c < 1 ? 1 : (c > MB_R ? MB_R : c);
@@ -206,18 +227,30 @@ inline int col_pack(int C) {
     return cp;
 }
 
-Plan make_plan(int B, int H0, int W0, int num_labels) {
+MbPlan mb_plan(int B, int H0, int W0, int num_labels, void* ws = nullptr) {
     const Net& n = net();
-    Plan p;
+    const int nl = (int)n.layers.size(), cus = howl_num_cus();
+    MbPlan p;
+    if (B < 1 || H0 < 1 || W0 < 1 || num_labels < 1) {
+        p.bad = "bad shape";
+        return p;
+    }
+    p.B = B;
+    p.ws = static_cast<float*>(ws);
+    p.L.resize(nl);
     size_t off = 0;
     auto take = [&](size_t floats) {
         const size_t o = off;
         off += (floats + 63) / 64 * 64;  // 256-byte granules
-        return o;
+        return (long)o;
     };
-    int h = H0, w = W0;
-    for (const HowlMbLayer& l : n.layers) {
-        Geo g{};
+    int h = H0, w = W0, sum_jobs = 1;      // (1: the downsample's conv-bias gradient)
+    bool fits = true;                      // every launch within the arrival counters and partial rows: MB_CBLOCKS x MB_R
+    for (int k = 0; k < nl; ++k) {
+        const HowlMbLayer& l = n.layers[k];
+        MbLayer& L = p.L[k];
+        Geo& g = L.g;
+        L.l = &l;
         g.hin = h;
         g.win = w;
         if (l.kind == MB_PW) {
@@ -231,33 +264,73 @@ Plan make_plan(int B, int H0, int W0, int num_labels) {
         g.wy = l.pool ? g.wo / 2 : g.wo;
         g.mz = (long)B * g.ho * g.wo;
         g.my = (long)B * g.hy * g.wy;
-        p.g.push_back(g);
-        p.z.push_back(take((size_t)g.mz * l.cout));
-        p.gr.push_back(take((size_t)g.mz * l.cout));
-        p.y.push_back(materialized(l) ? take((size_t)g.my * l.cout) : 0);
-        p.ss.push_back(take(4 * (size_t)l.cout));
-        p.bc.push_back(take(4 * (size_t)l.cout));
-        int ns;
+        L.z = take((size_t)g.mz * l.cout);
+        L.gr = take((size_t)g.mz * l.cout);
+        L.y = materialized(l) ? take((size_t)g.my * l.cout) : -1;
+        L.ss = take(4 * (size_t)l.cout);
+        L.bc = take(4 * (size_t)l.cout);
+        if (k > 0) {      // (the downsample layer reads x)
+            const MbLayer& P = p.L[k - 1];
+            const bool in_mat = materialized(*P.l);
+            L.b_in = L.f_in = in_mat ? P.y : P.z;
+            L.b_ss = L.f_ss = in_mat ? -1 : P.ss;
+            if (l.kind == MB_PW && in_mat) {
+                L.f_in = P.z;
+                L.f_ss = P.ss;
+                L.f_res = P.l->res_src >= 0 ? p.L[P.l->res_src].y : -1;
+                L.f_yout = P.y;
+            }
+        }
+        if (l.res_src >= 0) p.L[l.res_src].addend = L.gr;
         size_t wn;
         if (l.kind == MB_PW) {
-            const int rps = pw_wgrad_rows_per_split(g.mz, l.cout, l.cin);
-            ns = (int)((g.mz + rps - 1) / rps);
+            L.f_tile = pw_tile(g.mz, l.cout, cus);
+            L.f_cx = (l.cout + L.f_tile - 1) / L.f_tile;
+            pw_rows(g.mz, L.f_cx, &L.f_per, &L.f_ry, L.f_tile);
+            L.d_tile = pw_tile(g.mz, l.cin, cus);     // the data gradient's output is (M x cin)
+            L.d_cx = (l.cin + 63) / 64;
+            pw_rows(g.mz, L.d_cx, &L.tiles_per_block, &L.d_ry, L.d_tile);
+            L.rows_per_split = pw_wgrad_rows_per_split(g.mz, l.cout, l.cin);
+            L.w_cx = (l.cin + GT - 1) / GT;
+            L.w_ny = (l.cout + GT - 1) / GT;
+            L.nslab = (int)((g.mz + L.rows_per_split - 1) / L.rows_per_split);
+            fits = fits && L.d_cx <= MB_CBLOCKS && L.d_ry <= MB_R;
             wn = (size_t)l.cout * l.cin;
         } else if (l.kind == MB_DW) {
-            int per;
-            ns = row_chunks((long)B * g.ho, 8, &per);
+            L.f_cx = L.ncb = (l.cout + 63) / 64;
+            L.w_rows = (int)((long)B * g.ho);
+            L.d_rows = (int)((long)B * g.hin);
+            L.f_ry = row_chunks(L.w_rows, 4, &L.f_per);
+            L.d_chunks = row_chunks(L.d_rows, 4, &L.d_rpc);
+            L.nslab = row_chunks(L.w_rows, 8, &L.w_rpc);
+            fits = fits && L.d_chunks <= MB_R;
             wn = (size_t)l.cout * 9;
         } else {
-            ns = stem_blocks(g.mz);
+            L.f_cx = 1;
+            if (k == 0) {
+                L.f_ry = row_chunks(g.mz, 1024, &L.f_per);
+            } else {      // features[0]: the statistics are a launch of their own (col_stats_kernel)
+                L.cp = col_pack(l.cout);
+                L.f_ry = row_chunks(g.mz, 64 * (64 / L.cp), &L.f_per);
+                // data gradient of the downsample layer: four parity classes of its pooled pixels, <= MB_R blocks in all
+                const Geo& g0 = p.L[0].g;
+                const long per_class = (long)B * ((g0.ho + 1) / 2) * ((g0.wy + 1) / 2);
+                L.px_per_thread = (int)((per_class + 256L * (MB_R / 4) - 1) / (256L * (MB_R / 4)));
+                L.cls_blocks = (int)((per_class + 256L * L.px_per_thread - 1) / (256L * L.px_per_thread));
+                fits = fits && 4 * L.cls_blocks <= MB_R;
+            }
+            L.px_per_block = stem_px_per_block(g.mz);
+            L.nslab = (int)((g.mz + L.px_per_block - 1) / L.px_per_block);
             wn = (size_t)l.cout * l.cin * 9;
         }
-        p.nslab.push_back(ns);
-        p.slab.push_back(take((size_t)ns * wn));
+        fits = fits && L.f_cx <= MB_CBLOCKS && L.f_ry <= MB_R && l.cout <= MB_MAXC;
+        L.slab = take((size_t)L.nslab * wn);
+        ++sum_jobs;
         h = g.hy;
         w = g.wy;
     }
-    p.dz = take((size_t)p.g[1].mz * n.layers[1].cout);     // materialised dz of features[0]
-    p.slab0b = take((size_t)p.nslab[0] * n.layers[0].cout);  // conv-bias gradient slabs of the downsample layer
+    p.dz = take((size_t)p.L[1].g.mz * n.layers[1].cout);     // materialised dz of features[0]
+    p.slab0b = take((size_t)p.L[0].nslab * n.layers[0].cout);  // conv-bias gradient slabs of the downsample layer
     p.part = take((size_t)MB_R * 2 * MB_MAXC);
     p.part2 = take((size_t)MB_R2 * 2 * MB_MAXC);
     p.counters = take(MB_COUNTERS);
@@ -266,6 +339,13 @@ Plan make_plan(int B, int H0, int W0, int num_labels) {
     p.pooled = take((size_t)B * MB_LAST);
     p.pooled_d = take((size_t)B * MB_LAST);
     p.total_floats = off;
+    p.pool_chunks = row_chunks(B, 4, &p.pool_upc);
+
+    if (p.L[nl - 1].g.hy < 1 || p.L[nl - 1].g.wy < 1) p.bad = "input too small for the network";
+    else if (nl > MB_MAX_LAYERS) p.bad = "layer table too long";
+    else if (p.L[0].g.mz * 3 >= (1L << 31)) p.bad = "batch too large for the stem kernels' 32-bit pixel indices";
+    else if (sum_jobs > MB_MAX_JOBS) p.bad = "more deferred slab sums than MB_MAX_JOBS";
+    else if (!fits) p.bad = "a launch exceeds MB_CBLOCKS channel blocks or MB_R row blocks";
     return p;
 }
 
@@ -1947,7 +2027,7 @@ __global__ __launch_bounds__(256) void sum_jobs_kernel(MbSumJobs jobs) {
     __syncthreads();
     if (rg == 0 && i < n) jb.out[i] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
 }
-struct JobList {
+struct JobList {      // (mb_plan refuses a layer table with more sums than MB_MAX_JOBS)
     MbSumJobs jobs;
     JobList() { jobs.count = 0; jobs.blocks = 0; }
     void add(const float* part, int nparts, long n, float* out) {
@@ -1973,39 +2053,79 @@ inline unsigned flat_grid(long total) {
     return (unsigned)(blocks < 1 ? 1 : (blocks > 65536 ? 65536 : blocks));
 }
 
-struct Ctx {
-    const Net* n;
-    Plan p;
-    float* ws;
-    const float* params;
-    hipStream_t s;
-    int B;
-    unsigned* counters() const { return reinterpret_cast<unsigned*>(ws + p.counters); }
-    Arrive arrive() const { return Arrive{ws + p.part, ws + p.part2, counters(), counters() + MB_CBLOCKS * MB_R2}; }
-};
-
-StemGeo stem_geo(const Ctx& c) {
-    const Geo& g0 = c.p.g[0];
-    const Geo& g1 = c.p.g[1];
-    return StemGeo{c.B, g0.ho, g0.win, g0.wo, g0.wy, g1.ho, g1.wo};
+// ---- readers of the plan: the argument blocks that several kernels take by value ----
+unsigned* counters(const MbPlan& p) { return reinterpret_cast<unsigned*>(p.at(p.counters)); }
+Arrive arrive_of(const MbPlan& p) { return Arrive{p.at(p.part), p.at(p.part2), counters(p), counters(p) + MB_CBLOCKS * MB_R2}; }
+StemGeo stem_geo(const MbPlan& p) {
+    const Geo& g0 = p.L[0].g;
+    const Geo& g1 = p.L[1].g;
+    return StemGeo{p.B, g0.ho, g0.win, g0.wo, g0.wy, g1.ho, g1.wo};
 }
-
-FinFwd fin_fwd(const Ctx& c, int k, float* buffers) {
-    const HowlMbLayer& l = c.n->layers[k];
-    return FinFwd{c.params + l.gamma_off, c.params + l.beta_off, buffers + l.rmean_off, buffers + l.rvar_off,
-                  c.ws + c.p.ss[k], (double)c.p.g[k].mz};
+FinFwd fin_fwd(const MbPlan& p, int k, const float* params, float* buffers) {
+    const MbLayer& L = p.L[k];
+    return FinFwd{params + L.l->gamma_off, params + L.l->beta_off, buffers + L.l->rmean_off, buffers + L.l->rvar_off, p.at(L.ss),
+                  (double)L.g.mz};
 }
-FinBwd fin_bwd(const Ctx& c, int j, float* grads) {
-    const HowlMbLayer& l = c.n->layers[j];
-    return FinBwd{c.ws + c.p.ss[j], grads + l.gamma_off, grads + l.beta_off, c.ws + c.p.bc[j], (double)c.p.g[j].mz};
+FinBwd fin_bwd(const MbPlan& p, int j, float* grads) {
+    const MbLayer& L = p.L[j];
+    return FinBwd{p.at(L.ss), grads + L.l->gamma_off, grads + L.l->beta_off, p.at(L.bc), (double)L.g.mz};
 }
 // the epilogue of the kernel that produces layer j's incoming gradient
-EpiBwd epi_bwd(const Ctx& c, int j) {
-    const int nl = (int)c.n->layers.size();
-    const float* addend = nullptr;
-    for (int k2 = j + 1; k2 < nl; ++k2)
-        if (c.n->layers[k2].res_src == j) addend = c.ws + c.p.gr[k2];   // y_k2 = bn(z_k2) + y_j, no activation: dy_k2 = g_k2
-    return EpiBwd{addend, c.ws + c.p.z[j], c.ws + c.p.ss[j], c.ws + c.p.gr[j], c.n->layers[j].act};
+EpiBwd epi_bwd(const MbPlan& p, int j) {
+    const MbLayer& L = p.L[j];
+    return EpiBwd{p.at(L.addend), p.at(L.z), p.at(L.ss), p.at(L.gr), L.l->act};
+}
+
+// ---- launchers: per templated kernel ONE ladder that names its instances and maps layer k of the plan onto them ----
+void launch_pw_fwd(const MbPlan& p, int k, hipStream_t s, const float* params, const Arrive& arr, const FinFwd& fin) {
+    const MbLayer& L = p.L[k];
+    const float *in = p.at(L.f_in), *ss_in = p.at(L.f_ss), *w = params + L.l->w_off, *res = p.at(L.f_res);
+    float *y_out = p.at(L.f_yout), *z = p.at(L.z);
+    const bool linear = y_out != nullptr, t64 = L.f_tile == 64;      // 64 x 64 tiles, or 32 x 32
+    auto* kern = linear ? (t64 ? pw_fwd_kernel<PW_IN_LINEAR, 2, 2> : pw_fwd_kernel<PW_IN_LINEAR, 1, 1>)
+                        : (t64 ? pw_fwd_kernel<PW_IN_RELU6, 2, 2> : pw_fwd_kernel<PW_IN_RELU6, 1, 1>);
+    hipLaunchKernelGGL(kern, dim3(L.f_cx, L.f_ry), dim3(256), 0, s, in, ss_in, w, res, y_out, (int)L.g.mz, L.l->cout, L.l->cin,
+                       L.f_per, z, arr, fin);
+}
+void launch_dw_fwd(const MbPlan& p, int k, hipStream_t s, const float* params, const Arrive& arr, const FinFwd& fin) {
+    const MbLayer& L = p.L[k];
+    const Geo& g = L.g;
+    const float *in = p.at(L.f_in), *ss_in = p.at(L.f_ss), *w = params + L.l->w_off;
+    float* z = p.at(L.z);
+    auto* kern = L.l->stride == 1 ? dw_fwd_kernel<1> : dw_fwd_kernel<2>;
+    hipLaunchKernelGGL(kern, dim3(L.f_cx, L.f_ry), dim3(256), 0, s, in, ss_in, w, g.hin, g.win, L.l->cin, g.ho, g.wo, L.w_rows,
+                       L.f_per, z, arr, fin);
+}
+// backward of layer k >= 2 (the epilogue and BatchNorm backward are those of layer k-1); returns the slabs it wrote
+float* launch_pw_bwd(const MbPlan& p, int k, hipStream_t s, const float* params, float* grads, const Arrive& arr) {
+    const MbLayer& L = p.L[k];
+    const PwBwd a{p.at(L.gr), p.at(L.z), p.at(L.bc), params + L.l->w_off, p.at(L.b_in), p.at(L.b_ss),      // g zk bc w in ss_in
+                  (int)L.g.mz, L.l->cout, L.l->cin, L.tiles_per_block, L.d_cx, L.d_ry,                      // M N C, data gradient
+                  L.rows_per_split, L.w_cx, L.w_ny, L.nslab,                                                // weight gradient
+                  epi_bwd(p, k - 1), arr, fin_bwd(p, k - 1, grads), p.at(L.slab)};
+    const bool t64 = L.d_tile == 64;      // 64 x 64 data-gradient tiles, or 32 x 64
+    auto* kern = a.ss_in != nullptr ? (t64 ? pw_bwd_kernel<true, 2, 2> : pw_bwd_kernel<true, 1, 2>)
+                                    : (t64 ? pw_bwd_kernel<false, 2, 2> : pw_bwd_kernel<false, 1, 2>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(a.d_cx * a.d_ry + a.w_cx * a.w_ny * a.w_nz)), dim3(256), 0, s, a);
+    return a.slabs;
+}
+float* launch_dw_bwd(const MbPlan& p, int k, hipStream_t s, const float* params, float* grads, const Arrive& arr) {
+    const MbLayer& L = p.L[k];
+    const Geo& g = L.g;
+    const DwBwd a{p.at(L.gr), p.at(L.z), p.at(L.bc), params + L.l->w_off, p.at(L.b_in), p.at(L.b_ss),      // g zk bc w x ss_in
+                  g.hin, g.win, L.l->cin, g.ho, g.wo, L.ncb,                                                // H W C Ho Wo ncb
+                  L.d_rows, L.d_rpc, L.d_chunks, L.w_rows, L.w_rpc, L.nslab,                                // data, weight gradient
+                  epi_bwd(p, k - 1), arr, fin_bwd(p, k - 1, grads), p.at(L.slab)};
+    auto* kern = L.l->stride == 1 ? dw_bwd_kernel<1> : dw_bwd_kernel<2>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(a.ncb * (a.d_chunks + a.w_chunks))), dim3(256), 0, s, a);
+    return a.slabs;
+}
+
+// what both entry points refuse, with the caller's prefix
+int check_plan(const char* who, const MbPlan& p, size_t ws_bytes) {
+    HOWL_REQUIRE(p.bad == nullptr, "%s: %s", who, p.bad);
+    HOWL_REQUIRE(ws_bytes >= p.bytes(), "%s: workspace too small", who);
+    return HOWL_OK;
 }
 
 }  // namespace
@@ -2027,118 +2147,60 @@ size_t howl_mobilenet_param_floats(int num_labels) {
 
 size_t howl_mobilenet_buffer_floats(void) { return net().buffers; }
 
-size_t howl_mobilenet_workspace_bytes(int B, int M, int T, int num_labels) {
-    if (B < 1 || M < 1 || T < 1 || num_labels < 1) return 0;
-    return make_plan(B, M, T, num_labels).total_floats * sizeof(float) + 256;
-}
+size_t howl_mobilenet_workspace_bytes(int B, int M, int T, int num_labels) { return mb_plan(B, M, T, num_labels).bytes(); }
 
 int howl_mobilenet_fwd(const float* params, float* buffers, int num_labels, const float* x, long sb, long sm, long st, int B,
                        int M, int T, int training, const float* drop_mask, float drop_scale, float* logits, void* ws,
                        size_t ws_bytes, hipStream_t stream) {
     HOWL_REQUIRE(params && buffers && x && logits && ws, "howl_mobilenet_fwd: null pointer");
-    HOWL_REQUIRE(B >= 1 && M >= 1 && T >= 1 && num_labels >= 1, "howl_mobilenet_fwd: bad shape");
-    HOWL_REQUIRE(ws_bytes >= howl_mobilenet_workspace_bytes(B, M, T, num_labels), "howl_mobilenet_fwd: workspace too small");
-    Ctx c{&net(), make_plan(B, M, T, num_labels), reinterpret_cast<float*>(ws), params, stream, B};
-    const int nl = (int)c.n->layers.size();
-    HOWL_REQUIRE(c.p.g[nl - 1].hy >= 1 && c.p.g[nl - 1].wy >= 1, "howl_mobilenet_fwd: input too small for the network");
-    HOWL_REQUIRE(nl <= 64, "howl_mobilenet_fwd: layer table too long");
-    HOWL_REQUIRE(c.p.g[0].mz * 3 < (1L << 31), "howl_mobilenet_fwd: batch too large for the stem kernels' 32-bit pixel indices");
-    Arrive arr = c.arrive();
+    const MbPlan p = mb_plan(B, M, T, num_labels, ws);
+    if (const int rc = check_plan("howl_mobilenet_fwd", p, ws_bytes)) return rc;
+    const int nl = (int)p.L.size();
+    Arrive arr = arrive_of(p);
     if (!training) arr.part1 = nullptr;     // no statistics: ss comes from the running estimates
-    hipMemsetAsync(c.counters(), 0, MB_COUNTERS * sizeof(unsigned), stream);
+    hipMemsetAsync(counters(p), 0, MB_COUNTERS * sizeof(unsigned), stream);
     if (!training) {
         EvalJobs jobs{};
         for (int k = 0; k < nl; ++k) {
-            const HowlMbLayer& l = c.n->layers[k];
+            const HowlMbLayer& l = *p.L[k].l;
             jobs.c[k] = l.cout;
             jobs.gamma_off[k] = l.gamma_off;
             jobs.rmean_off[k] = l.rmean_off;
-            jobs.ss_off[k] = (long long)c.p.ss[k];
+            jobs.ss_off[k] = p.L[k].ss;
         }
         hipLaunchKernelGGL(bn_eval_ss_kernel, dim3((MB_MAXC + 255) / 256, nl), dim3(256), 0, stream, jobs, params,
-                           (const float*)buffers, c.ws);
+                           (const float*)buffers, p.ws);
     }
     for (int k = 0; k < nl; ++k) {
-        const HowlMbLayer& l = c.n->layers[k];
-        const Geo& g = c.p.g[k];
-        float* z = c.ws + c.p.z[k];
-        // the layer's input: y_{k-1} where it exists, else z_{k-1} with the BatchNorm + ReLU6 of layer k-1 applied on load
-        const bool in_mat = k == 0 || materialized(c.n->layers[k - 1]);   // (the stem kernels find their own inputs)
-        const float* in = k == 0 ? x : (in_mat ? c.ws + c.p.y[k - 1] : c.ws + c.p.z[k - 1]);
-        const float* ss_in = in_mat ? nullptr : c.ws + c.p.ss[k - 1];
-        const FinFwd fin = fin_fwd(c, k, buffers);
+        const MbLayer& L = p.L[k];
+        const HowlMbLayer& l = *L.l;
+        const Geo& g = L.g;
+        const FinFwd fin = fin_fwd(p, k, params, buffers);
         if (l.kind == MB_PW) {
-            // layers whose 64 x 64 tiles would leave CUs idle (the late, deep-reduction bottleneck layers: 96-192 tiles) take
-            // 32 x 32 tiles: four times the blocks, a quarter of the MFMA chain per step
-            const int tile = pw_tile(g.mz, l.cout);
-            const int tc = tile == 32 ? env_int("HOWL_MB_FWD_TC", 32) : 64;    // tile columns (rows = `tile`)
-            int tpb, rb;
-            pw_rows(g.mz, (l.cout + tc - 1) / tc, &tpb, &rb, tile);
-            const dim3 grid((l.cout + tc - 1) / tc, rb);
             HowlProfScope prof("mb_conv", stream, 4.0 * (double)g.mz * (l.cin + l.cout));
-            const HowlMbLayer& lp = c.n->layers[k - 1];
-            const float* res = nullptr;
-            float* y_out = nullptr;
-            const float* src = in;
-            const float* ssp = ss_in;
-            if (in_mat) {     // y_{k-1} = bn(z_{k-1}) (+ y_res) is built here, on load, and stored for its later readers
-                src = c.ws + c.p.z[k - 1];
-                ssp = c.ws + c.p.ss[k - 1];
-                res = lp.res_src >= 0 ? c.ws + c.p.y[lp.res_src] : nullptr;
-                y_out = c.ws + c.p.y[k - 1];
-            }
-#define HOWL_PW_FWD(XF)                                                                                                   \
-    do {                                                                                                                  \
-        if (tile == 64)                                                                                                      \
-            hipLaunchKernelGGL((pw_fwd_kernel<XF, 2, 2>), grid, dim3(256), 0, stream, src, ssp, params + l.w_off, res, \
-                               y_out, (int)g.mz, l.cout, l.cin, tpb, z, arr, fin);                                           \
-        else if (tc == 64)                                                                                                   \
-            hipLaunchKernelGGL((pw_fwd_kernel<XF, 1, 2>), grid, dim3(256), 0, stream, src, ssp, params + l.w_off, res, \
-                               y_out, (int)g.mz, l.cout, l.cin, tpb, z, arr, fin);                                           \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((pw_fwd_kernel<XF, 1, 1>), grid, dim3(256), 0, stream, src, ssp, params + l.w_off, res, \
-                               y_out, (int)g.mz, l.cout, l.cin, tpb, z, arr, fin);                                           \
-    } while (0)
-            if (!in_mat) HOWL_PW_FWD(PW_IN_RELU6);
-            else HOWL_PW_FWD(PW_IN_LINEAR);
-#undef HOWL_PW_FWD
+            launch_pw_fwd(p, k, stream, params, arr, fin);
         } else if (l.kind == MB_DW) {
-            int rpc;
-            const int nrows = B * g.ho;
-            const int chunks = row_chunks(nrows, 4, &rpc);
-            const dim3 grid((l.cout + 63) / 64, chunks);
             HowlProfScope prof("mb_conv", stream, 4.0 * ((double)B * g.hin * g.win + (double)g.mz) * l.cout);
-            if (l.stride == 1)
-                hipLaunchKernelGGL(dw_fwd_kernel<1>, grid, dim3(256), 0, stream, in, ss_in, params + l.w_off, g.hin, g.win, l.cin,
-                                   g.ho, g.wo, nrows, rpc, z, arr, fin);
-            else
-                hipLaunchKernelGGL(dw_fwd_kernel<2>, grid, dim3(256), 0, stream, in, ss_in, params + l.w_off, g.hin, g.win, l.cin,
-                                   g.ho, g.wo, nrows, rpc, z, arr, fin);
+            launch_dw_fwd(p, k, stream, params, arr, fin);
         } else if (k == 0) {
-            int ppb;
-            const int chunks = row_chunks(g.mz, 1024, &ppb);
-            hipLaunchKernelGGL(stem0_fwd_kernel, dim3(1, chunks), dim3(256), 0, stream, x, sb, sm, st, params + l.w_off,
-                               params + l.b_off, stem_geo(c), g.mz, ppb, z, arr, fin);
+            hipLaunchKernelGGL(stem0_fwd_kernel, dim3(1, L.f_ry), dim3(256), 0, stream, x, sb, sm, st, params + l.w_off,
+                               params + l.b_off, stem_geo(p), g.mz, L.f_per, p.at(L.z), arr, fin);
         } else {
             hipLaunchKernelGGL(stem1_fwd_kernel, dim3((unsigned)((g.mz + 255) / 256)), dim3(256), 0, stream,
-                               (const float*)(c.ws + c.p.z[0]), (const float*)(c.ws + c.p.ss[0]), params + l.w_off, stem_geo(c),
-                               g.mz, z);
-            if (training) {
-                int rpc;
-                const int cp = col_pack(l.cout);
-                const int chunks = row_chunks(g.mz, 64 * (64 / cp), &rpc);
-                hipLaunchKernelGGL(col_stats_kernel, dim3(1, chunks), dim3(256), 0, stream, (const float*)z, g.mz, l.cout, cp,
-                                   (long)rpc, arr, fin);
-            }
+                               (const float*)p.at(p.L[0].z), (const float*)p.at(p.L[0].ss), params + l.w_off, stem_geo(p), g.mz,
+                               p.at(L.z));
+            if (training)
+                hipLaunchKernelGGL(col_stats_kernel, dim3(1, L.f_ry), dim3(256), 0, stream, (const float*)p.at(L.z), g.mz, l.cout,
+                                   L.cp, (long)L.f_per, arr, fin);
         }
     }
-    const Geo& gl = c.p.g[nl - 1];
-    const float* wc = params + c.n->feature_params;
+    const MbLayer& last = p.L[nl - 1];
+    const float* wc = params + net().feature_params;
     const float* bcl = wc + (size_t)num_labels * MB_LAST;
     static_assert(MB_LAST <= 256 * POOL_CPT, "pool_classify_kernel: channels per block");
-    hipLaunchKernelGGL(pool_classify_kernel, dim3((unsigned)B), dim3(256), 0, stream, (const float*)(c.ws + c.p.z[nl - 1]),
-                       (const float*)(c.ws + c.p.ss[nl - 1]), gl.hy * gl.wy, MB_LAST, training ? drop_mask : (const float*)nullptr,
-                       drop_scale, wc, bcl, num_labels, c.ws + c.p.pooled, c.ws + c.p.pooled_d, logits);
+    hipLaunchKernelGGL(pool_classify_kernel, dim3((unsigned)B), dim3(256), 0, stream, (const float*)p.at(last.z),
+                       (const float*)p.at(last.ss), last.g.hy * last.g.wy, MB_LAST, training ? drop_mask : (const float*)nullptr,
+                       drop_scale, wc, bcl, num_labels, p.at(p.pooled), p.at(p.pooled_d), logits);
     HOWL_CHECK_LAUNCH("howl_mobilenet_fwd");
     return HOWL_OK;
 }
@@ -2147,142 +2209,63 @@ int howl_mobilenet_bwd(const float* params, int num_labels, const float* x, long
                        const float* drop_mask, float drop_scale, const float* dlogits, float* grads, void* ws, size_t ws_bytes,
                        hipStream_t stream) {
     HOWL_REQUIRE(params && x && dlogits && grads && ws, "howl_mobilenet_bwd: null pointer");
-    HOWL_REQUIRE(B >= 1 && M >= 1 && T >= 1 && num_labels >= 1, "howl_mobilenet_bwd: bad shape");
-    HOWL_REQUIRE(ws_bytes >= howl_mobilenet_workspace_bytes(B, M, T, num_labels), "howl_mobilenet_bwd: workspace too small");
-    Ctx c{&net(), make_plan(B, M, T, num_labels), reinterpret_cast<float*>(ws), params, stream, B};
-    const int nl = (int)c.n->layers.size();
-    const Arrive arr = c.arrive();
-    hipMemsetAsync(c.counters(), 0, MB_COUNTERS * sizeof(unsigned), stream);
+    const MbPlan p = mb_plan(B, M, T, num_labels, ws);
+    if (const int rc = check_plan("howl_mobilenet_bwd", p, ws_bytes)) return rc;
+    const int nl = (int)p.L.size();
+    const Arrive arr = arrive_of(p);
+    hipMemsetAsync(counters(p), 0, MB_COUNTERS * sizeof(unsigned), stream);
     // One launch per layer: the data gradient of layer k (which also reduces the BatchNorm backward of the layer in front,
     // so layer k-1's dz exists -- as g, z, bc -- the moment the launch ends) and the weight gradient of layer k share a grid.
     JobList jobs;     // every weight gradient's slab sum, one launch at the end
     SlabSums head;    // classifier
     // classifier: logits = pooled_d W^T + b
-    const float* wc = params + c.n->feature_params;
-    float* gwc = grads + c.n->feature_params;
+    const float* wc = params + net().feature_params;
+    float* gwc = grads + net().feature_params;
     float* gbc = gwc + (size_t)num_labels * MB_LAST;
     {
         // gradient of the pooled features -> g, bc of the last layer
-        const int L = nl - 1;
-        const Geo& gl = c.p.g[L];
-        int upc;
-        const int chunks = row_chunks(B, 4, &upc);
-        hipLaunchKernelGGL(avgpool_bwd_reduce_kernel, dim3((MB_LAST + 63) / 64, chunks), dim3(256), 0, stream,
-                           dlogits, wc, num_labels, drop_mask, drop_scale, gl.hy * gl.wy, MB_LAST, B, upc, epi_bwd(c, L), arr,
-                           fin_bwd(c, L, grads));
+        const int last = nl - 1;
+        const Geo& gl = p.L[last].g;
+        static_assert((MB_LAST + 63) / 64 <= MB_CBLOCKS, "avgpool_bwd_reduce_kernel: channel blocks");
+        hipLaunchKernelGGL(avgpool_bwd_reduce_kernel, dim3((MB_LAST + 63) / 64, p.pool_chunks), dim3(256), 0, stream, dlogits, wc,
+                           num_labels, drop_mask, drop_scale, gl.hy * gl.wy, MB_LAST, B, p.pool_upc, epi_bwd(p, last), arr,
+                           fin_bwd(p, last, grads));
     }
-    wgrad_gemm(stream, dlogits, lin(num_labels), num_labels, c.ws + c.p.pooled_d, lin(MB_LAST), MB_LAST, B,
-               c.ws + c.p.head_scratch, gwc, 64, 512, &head);
-    colsum(stream, dlogits, lin(num_labels), B, num_labels, c.ws + c.p.bias_scratch, gbc, nullptr, 64, 256, &head);
+    wgrad_gemm(stream, dlogits, lin(num_labels), num_labels, p.at(p.pooled_d), lin(MB_LAST), MB_LAST, B, p.at(p.head_scratch), gwc,
+               64, 512, &head);
+    colsum(stream, dlogits, lin(num_labels), B, num_labels, p.at(p.bias_scratch), gbc, nullptr, 64, 256, &head);
     for (int k = nl - 1; k >= 2; --k) {
-        const HowlMbLayer& l = c.n->layers[k];
-        const Geo& g = c.p.g[k];
-        const int j = k - 1;
-        const HowlMbLayer& lj = c.n->layers[j];
-        const bool in_mat = materialized(lj);
-        const float* in = in_mat ? c.ws + c.p.y[j] : c.ws + c.p.z[j];
-        const float* ss_in = in_mat ? nullptr : c.ws + c.p.ss[j];
-        float* slab = c.ws + c.p.slab[k];
+        const MbLayer& L = p.L[k];
+        const HowlMbLayer& l = *L.l;
+        const Geo& g = L.g;
         if (l.kind == MB_PW) {
-            PwBwd a{};
-            a.g = c.ws + c.p.gr[k];
-            a.zk = c.ws + c.p.z[k];
-            a.bc = c.ws + c.p.bc[k];
-            a.w = params + l.w_off;
-            a.in = in;
-            a.ss_in = ss_in;
-            a.M = (int)g.mz;
-            a.N = l.cout;
-            a.C = l.cin;
-            const int tile = pw_tile(g.mz, l.cin);     // the data gradient's output is (M x cin)
-            const int tc = tile == 32 ? env_int("HOWL_MB_BWD_TC", 64) : 64;
-            a.d_cx = (l.cin + tc - 1) / tc;
-            pw_rows(g.mz, a.d_cx, &a.tiles_per_block, &a.d_ry, tile);
-            a.rows_per_split = pw_wgrad_rows_per_split(g.mz, l.cout, l.cin);
-            a.w_cx = (l.cin + GT - 1) / GT;
-            a.w_ny = (l.cout + GT - 1) / GT;
-            a.w_nz = (int)((g.mz + a.rows_per_split - 1) / a.rows_per_split);
-            a.e = epi_bwd(c, j);
-            a.arr = arr;
-            a.fin = fin_bwd(c, j, grads);
-            a.slabs = slab;
-            const unsigned blocks = (unsigned)(a.d_cx * a.d_ry + a.w_cx * a.w_ny * a.w_nz);
             HowlProfScope prof("mb_conv", stream, 4.0 * (double)g.mz * (4.0 * l.cout + 4.0 * l.cin));
-#define HOWL_PW_BWD(XF)                                                                                     \
-    do {                                                                                                    \
-        if (tile == 64) hipLaunchKernelGGL((pw_bwd_kernel<XF, 2, 2>), dim3(blocks), dim3(256), 0, stream, a);       \
-        else if (tc == 64) hipLaunchKernelGGL((pw_bwd_kernel<XF, 1, 2>), dim3(blocks), dim3(256), 0, stream, a);    \
-        else hipLaunchKernelGGL((pw_bwd_kernel<XF, 1, 1>), dim3(blocks), dim3(256), 0, stream, a);                  \
-    } while (0)
-            if (ss_in != nullptr) HOWL_PW_BWD(true);
-            else HOWL_PW_BWD(false);
-#undef HOWL_PW_BWD
-            jobs.add(slab, a.w_nz, (long)l.cout * l.cin, grads + l.w_off);
+            jobs.add(launch_pw_bwd(p, k, stream, params, grads, arr), L.nslab, (long)l.cout * l.cin, grads + l.w_off);
         } else {   // depthwise (layers 0 and 1 are the only dense ones)
-            DwBwd a{};
-            a.g = c.ws + c.p.gr[k];
-            a.zk = c.ws + c.p.z[k];
-            a.bc = c.ws + c.p.bc[k];
-            a.w = params + l.w_off;
-            a.x = in;
-            a.ss_in = ss_in;
-            a.H = g.hin;
-            a.W = g.win;
-            a.C = l.cin;
-            a.Ho = g.ho;
-            a.Wo = g.wo;
-            a.ncb = (l.cout + 63) / 64;
-            a.d_rows = B * g.hin;
-            a.d_chunks = row_chunks(a.d_rows, 4, &a.d_rpc);
-            a.w_rows = B * g.ho;
-            a.w_chunks = row_chunks(a.w_rows, 8, &a.w_rpc);
-            a.e = epi_bwd(c, j);
-            a.arr = arr;
-            a.fin = fin_bwd(c, j, grads);
-            a.slabs = slab;
-            const unsigned blocks = (unsigned)(a.ncb * (a.d_chunks + a.w_chunks));
             HowlProfScope prof("mb_conv", stream, 4.0 * (4.0 * (double)g.mz + 3.0 * (double)B * g.hin * g.win) * l.cout);
-            if (l.stride == 1)
-                hipLaunchKernelGGL(dw_bwd_kernel<1>, dim3(blocks), dim3(256), 0, stream, a);
-            else
-                hipLaunchKernelGGL(dw_bwd_kernel<2>, dim3(blocks), dim3(256), 0, stream, a);
-            jobs.add(slab, a.w_chunks, (long)l.cout * 9, grads + l.w_off);
+            jobs.add(launch_dw_bwd(p, k, stream, params, grads, arr), L.nslab, (long)l.cout * 9, grads + l.w_off);
         }
     }
     // ---- stem ---------------------------------------------------------------------------------------------------------
     {
-        const HowlMbLayer& l0 = c.n->layers[0];
-        const HowlMbLayer& l1 = c.n->layers[1];
-        const Geo& g0 = c.p.g[0];
-        const Geo& g1 = c.p.g[1];
-        const StemGeo sg = stem_geo(c);
-        float* dz1 = c.ws + c.p.dz;
-        const long t1 = g1.mz * l1.cout;
-        hipLaunchKernelGGL(dz_apply_kernel, dim3(flat_grid(t1)), dim3(256), 0, stream, (const float*)(c.ws + c.p.gr[1]),
-                           (const float*)(c.ws + c.p.z[1]), (const float*)(c.ws + c.p.bc[1]), l1.cout, t1, dz1);
-        Stem1Bwd a{};
-        a.dz1 = dz1;
-        a.z0 = c.ws + c.p.z[0];
-        a.ss0 = c.ws + c.p.ss[0];
-        a.w = params + l1.w_off;
-        a.s = sg;
-        a.px_per_wblock = stem_px_per_block(g1.mz);
-        a.wblocks = stem_blocks(g1.mz);
-        const long per_class = (long)B * ((sg.H + 1) / 2) * ((sg.Wp + 1) / 2);
-        a.px_per_thread = (int)((per_class + 256L * (MB_R / 4) - 1) / (256L * (MB_R / 4)));
-        a.cls_blocks = (int)((per_class + 256L * a.px_per_thread - 1) / (256L * a.px_per_thread));
-        a.slabs = c.ws + c.p.slab[1];
-        a.g0 = c.ws + c.p.gr[0];
-        a.arr = arr;
-        a.fin = fin_bwd(c, 0, grads);
+        const MbLayer& L0 = p.L[0];
+        const MbLayer& L1 = p.L[1];
+        const HowlMbLayer& l0 = *L0.l;
+        const HowlMbLayer& l1 = *L1.l;
+        const StemGeo sg = stem_geo(p);
+        float* dz1 = p.at(p.dz);
+        const long t1 = L1.g.mz * l1.cout;
+        hipLaunchKernelGGL(dz_apply_kernel, dim3(flat_grid(t1)), dim3(256), 0, stream, (const float*)p.at(L1.gr),
+                           (const float*)p.at(L1.z), (const float*)p.at(L1.bc), l1.cout, t1, dz1);
+        const Stem1Bwd a{dz1, p.at(L0.z), p.at(L0.ss), params + l1.w_off, sg, L1.nslab, L1.px_per_block,      // .. wblocks px_per_wblock
+                         L1.cls_blocks, L1.px_per_thread, p.at(L1.slab), p.at(L0.gr), arr, fin_bwd(p, 0, grads)};
         hipLaunchKernelGGL(stem1_bwd_kernel, dim3((unsigned)(a.wblocks + 4 * a.cls_blocks)), dim3(256), 0, stream, a);
-        jobs.add(a.slabs, a.wblocks, (long)l1.cout * l1.cin * 9, grads + l1.w_off);
-        const int nb0 = stem_blocks(g0.mz);
-        hipLaunchKernelGGL(stem0_bwd_kernel, dim3((unsigned)nb0), dim3(256), 0, stream, x, sb, sm, st,
-                           (const float*)(c.ws + c.p.gr[0]), (const float*)(c.ws + c.p.z[0]), (const float*)(c.ws + c.p.bc[0]), sg,
-                           g0.mz, stem_px_per_block(g0.mz), c.ws + c.p.slab[0], c.ws + c.p.slab0b);
-        jobs.add(c.ws + c.p.slab[0], nb0, (long)l0.cout * l0.cin * 9, grads + l0.w_off);
-        jobs.add(c.ws + c.p.slab0b, nb0, (long)l0.cout, grads + l0.b_off);
+        jobs.add(a.slabs, L1.nslab, (long)l1.cout * l1.cin * 9, grads + l1.w_off);
+        hipLaunchKernelGGL(stem0_bwd_kernel, dim3((unsigned)L0.nslab), dim3(256), 0, stream, x, sb, sm, st,
+                           (const float*)p.at(L0.gr), (const float*)p.at(L0.z), (const float*)p.at(L0.bc), sg, L0.g.mz,
+                           L0.px_per_block, p.at(L0.slab), p.at(p.slab0b));
+        jobs.add(p.at(L0.slab), L0.nslab, (long)l0.cout * l0.cin * 9, grads + l0.w_off);
+        jobs.add(p.at(p.slab0b), L0.nslab, (long)l0.cout, grads + l0.b_off);
     }
     if (!head.flush(stream)) return HOWL_E_ARG;
     jobs.flush(stream);

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from emu_util import emu_lib, ptr
-from howl_amd.lib import HowlMbLayer
+from howl_amd.lib import HowlHipError, HowlMbLayer
 from mb_util import check_grads, oracle_step
 from oracle import mobilenet as om
 
@@ -124,3 +124,15 @@ def test_forward_backward_vs_oracle(lib, B, T, dropout):
             off += n
     eref = om.mobilenet_forward(esd, x, False)
     np.testing.assert_allclose(elog, eref.numpy(), rtol=0, atol=5e-5)
+
+    # what the launch plan refuses, both directions refuse, with the same reason and before anything is launched
+    Bx, Mx, Tx = 512, 80, 20000
+    with pytest.raises(HowlHipError, match=r"howl_mobilenet_fwd: batch too large for the stem kernels"):
+        lib.call("howl_mobilenet_fwd", ptr(flat), ptr(bufs), C, ptr(xn), sb, sm, st, Bx, Mx, Tx, 1, ptr(mask), scale, ptr(logits),
+                 ptr(ws), ws.size, None)
+    with pytest.raises(HowlHipError, match=r"howl_mobilenet_bwd: batch too large for the stem kernels"):
+        lib.call("howl_mobilenet_bwd", ptr(flat), C, ptr(xn), sb, sm, st, Bx, Mx, Tx, ptr(mask), scale, ptr(dlogits), ptr(g), ptr(ws),
+                 ws.size, None)
+    with pytest.raises(HowlHipError, match=r"howl_mobilenet_bwd: bad shape"):
+        lib.call("howl_mobilenet_bwd", ptr(flat), C, ptr(xn), sb, sm, st, B, M, 0, ptr(mask), scale, ptr(dlogits), ptr(g), ptr(ws),
+                 ws.size, None)
