@@ -2149,6 +2149,45 @@ size_t howl_mobilenet_buffer_floats(void) { return net().buffers; }
 
 size_t howl_mobilenet_workspace_bytes(int B, int M, int T, int num_labels) { return mb_plan(B, M, T, num_labels).bytes(); }
 
+int howl_mobilenet_workspace_layer(int B, int M, int T, int num_labels, int i, HowlMbWsLayer* out) {
+    HOWL_REQUIRE(out != nullptr, "howl_mobilenet_workspace_layer: null pointer");
+    const MbPlan p = mb_plan(B, M, T, num_labels);
+    HOWL_REQUIRE(p.bad == nullptr, "howl_mobilenet_workspace_layer: %s", p.bad);
+    HOWL_REQUIRE(i >= 0 && i <= (int)p.L.size(), "howl_mobilenet_workspace_layer: index out of range");
+    HowlMbWsLayer o{};
+    o.z = o.g = o.y = o.ss = o.bc = o.b_ss = o.f_yout = -1;
+    o.pooled = p.pooled;
+    o.pooled_d = p.pooled_d;
+    o.dz1 = p.dz;
+    o.total_floats = (long long)p.total_floats;
+    o.group_rows = MB_R2;
+    if (i < (int)p.L.size()) {
+        const MbLayer& L = p.L[i];
+        o.z = L.z;
+        o.g = L.gr;
+        o.y = L.y;
+        o.ss = L.ss;
+        o.bc = L.bc;
+        o.b_ss = L.b_ss;
+        o.f_yout = L.f_yout;
+        o.hin = L.g.hin;
+        o.win = L.g.win;
+        o.ho = L.g.ho;
+        o.wo = L.g.wo;
+        o.hy = L.g.hy;
+        o.wy = L.g.wy;
+        o.f_tile = L.f_tile;
+        o.f_cx = L.f_cx;
+        o.f_ry = L.f_ry;
+        o.d_tile = L.d_tile;
+        o.d_ry = L.d_ry;
+        o.d_chunks = L.d_chunks;
+        o.nslab = L.nslab;
+    }
+    *out = o;
+    return HOWL_OK;
+}
+
 int howl_mobilenet_fwd(const float* params, float* buffers, int num_labels, const float* x, long sb, long sm, long st, int B,
                        int M, int T, int training, const float* drop_mask, float drop_scale, float* logits, void* ws,
                        size_t ws_bytes, hipStream_t stream) {

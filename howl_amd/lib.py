@@ -82,6 +82,13 @@ class HowlMbLayer(ctypes.Structure):
                [(n, ctypes.c_longlong) for n in ("w_off", "b_off", "gamma_off", "beta_off", "rmean_off", "rvar_off")]
 
 
+class HowlMbWsLayer(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_longlong) for n in ("z", "g", "y", "ss", "bc", "b_ss", "f_yout", "pooled", "pooled_d", "dz1",
+                                                 "total_floats")] + \
+               [(n, c_int) for n in ("hin", "win", "ho", "wo", "hy", "wy", "f_tile", "f_cx", "f_ry", "d_tile", "d_ry", "d_chunks",
+                                     "nslab", "group_rows")]
+
+
 SIGNATURES = {
     "howl_version": [POINTER(c_int), POINTER(c_int)],
     "howl_profile_enable": [c_int],
@@ -134,6 +141,7 @@ SIGNATURES = {
                           POINTER(HowlLstmGrads), P, c_size_t, POINTER(HowlAdamW), STREAM],
     "howl_adamw_step": [P, P, P, P, c_size_t, c_float, c_float, c_float, c_float, c_float, c_int, c_float, STREAM],
     "howl_mobilenet_layer": [c_int, POINTER(HowlMbLayer)],
+    "howl_mobilenet_workspace_layer": [c_int, c_int, c_int, c_int, c_int, POINTER(HowlMbWsLayer)],
     "howl_mobilenet_fwd": [P, P, c_int, P, c_long, c_long, c_long, c_int, c_int, c_int, c_int, P, c_float, P, P, c_size_t,
                            STREAM],
     "howl_mobilenet_bwd": [P, c_int, P, c_long, c_long, c_long, c_int, c_int, c_int, P, c_float, P, P, P, c_size_t, STREAM],

@@ -433,6 +433,24 @@ int howl_mobilenet_layer(int i, HowlMbLayer* out);
 size_t howl_mobilenet_param_floats(int num_labels);
 size_t howl_mobilenet_buffer_floats(void);
 size_t howl_mobilenet_workspace_bytes(int B, int M, int T, int num_labels);
+/* Introspection for tests and tools; launches nothing and touches no memory but *out.  Where howl_mobilenet_fwd (training) and
+ * howl_mobilenet_bwd leave layer i of problem (B, M, T, num_labels) in the workspace, and the launch shapes that say which kernel
+ * instance ran, all read from the same launch plan the two entry points use: float offsets from the workspace start of z_i
+ * (convolution output, (B, ho, wo, cout) channels-last), g_i (masked incoming gradient, same shape), y_i ((B, hy, wy, cout), -1
+ * unless stored), ss_i ([scale | shift | mean | rstd], 4 cout) and bc_i ([scale | c1 | c0], 3 cout); b_ss: the ss operand the
+ * layer's backward launch applies to its input on load (-1: it reads a stored y); f_yout: the y a pointwise forward stores for
+ * its producer (-1: none).  Launch shapes (0 where the kind has none): pointwise forward f_tile (32 / 64) x f_cx x f_ry blocks,
+ * data gradient d_tile x d_ry; depthwise / stem f_ry forward chunks, depthwise d_chunks; nslab weight-gradient slabs.  group_rows:
+ * launches with more row blocks than this fold their per-channel partial sums in two levels.  The tail fields (pooled, pooled_d:
+ * (B, 1280); dz1: the materialised dz of features[0]; total_floats) are filled for every i, and i == howl_mobilenet_num_layers()
+ * returns them alone.  Refuses what the plan refuses, with the plan's reason. */
+typedef struct {
+    long long z, g, y, ss, bc, b_ss, f_yout;
+    long long pooled, pooled_d, dz1, total_floats;
+    int hin, win, ho, wo, hy, wy;
+    int f_tile, f_cx, f_ry, d_tile, d_ry, d_chunks, nslab, group_rows;
+} HowlMbWsLayer;
+int howl_mobilenet_workspace_layer(int B, int M, int T, int num_labels, int i, HowlMbWsLayer* out);
 /* n keep flags (1.0 with probability 1 - p, else 0.0) from the counter-based device generator keyed by `seed`: the
  * drop_mask operand of howl_mobilenet_fwd / _bwd, replacing nn.Dropout's torch.rand chain (cnn.py:22 via torchvision's classifier). */
 int howl_dropout_mask(float* mask, size_t n, float p, unsigned long long seed, hipStream_t stream);

@@ -31,6 +31,7 @@ EXEMPT = {
     "howl_shutdown": "releases side queues and events",
     "howl_seq_head_ctc_supported": "range query",
     "howl_mobilenet_layer": "host layer table",
+    "howl_mobilenet_workspace_layer": "host query of the launch plan (workspace map)",
 }
 PLACEMENTS = ("tail", "head")
 TIMEOUT = 900

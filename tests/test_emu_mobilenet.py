@@ -2,6 +2,7 @@
 (oracle/mobilenet.py; parity unpinned against torchvision -- see its header): layer table, forward in training and
 eval mode, BatchNorm buffer updates, every parameter gradient."""
 import ctypes
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -9,6 +10,7 @@ import torch
 
 from emu_util import emu_lib, ptr
 from howl_amd.lib import HowlHipError, HowlMbLayer
+import mb_layerwise as ml
 from mb_util import check_grads, oracle_step
 from oracle import mobilenet as om
 
@@ -136,3 +138,82 @@ def test_forward_backward_vs_oracle(lib, B, T, dropout):
     with pytest.raises(HowlHipError, match=r"howl_mobilenet_bwd: bad shape"):
         lib.call("howl_mobilenet_bwd", ptr(flat), C, ptr(xn), sb, sm, st, B, M, 0, ptr(mask), scale, ptr(dlogits), ptr(g), ptr(ws),
                  ws.size, None)
+
+
+# ---- layer-local float64 checks (tests/mb_layerwise.py) --------------------------------------------------------------------
+# (B, M, T, labels, dropout, layout of x, also eval mode).  (5, 40, 30): the shape of the oracle comparison above, with dropout;
+# (3, 33, 27): odd mel count, nothing divides; (2, 80, 21): 80 mel bins; x as (B, T, M) frames -- st = M, sm = 1, slack between
+# utterances -- with 3 labels (13 x 40 x 9: 65 row chunks in the first depthwise data gradient, so the two-level fold runs) and with 35.
+LAYERWISE = [(5, 40, 30, 5, True, "bmt", True), (3, 33, 27, 5, False, "bmt", False), (2, 80, 21, 5, False, "bmt", False),
+             (13, 40, 9, 3, True, "btm", False), (2, 40, 37, 35, False, "btm", False)]
+BIG_DEVICE = (5, 40, 30, 5, True, "bmt")      # once more on an emulated 256-CU device: 32-row forward and 32 x 64 data-gradient tiles
+
+
+def _child(mode, case, cus):
+    import json
+    import os
+    import subprocess
+    import sys
+    here = Path(__file__).resolve().parent
+    python = [sys.executable] + [flag for flag, on in (("-s", sys.flags.no_user_site), ("-E", sys.flags.ignore_environment)) if on]
+    env = dict(os.environ, HIPEMU_CUS=str(cus), PYTHONPATH=os.pathsep.join([str(here.parent), str(here)]))
+    r = subprocess.run(python + [str(here / "mb_layerwise.py"), mode] + [str(int(v)) for v in case[:5]] + [case[5]], env=env,
+                       capture_output=True, text=True, timeout=2400, cwd=here.parent)
+    print(r.stdout)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-6000:]
+    return json.loads(r.stdout.split("RESULT", 1)[1])
+
+
+@pytest.mark.parametrize("B,M,T,C,dropout,layout,eval_too", LAYERWISE)
+def test_every_layer_vs_float64(lib, B, M, T, C, dropout, layout, eval_too):
+    """Every layer's forward and backward, each from the kernels' own neighbouring tensors, against float64 (see mb_layerwise)."""
+    ml.run_case(lib, ml.HostMem(), B, M, T, C, dropout, layout, eval_too=eval_too)
+
+
+def test_every_layer_vs_float64_on_256_cus():
+    out = _child("check", BIG_DEVICE, 256)
+    assert "training" in out["reports"]
+
+
+def test_layerwise_cases_cover_the_kernel_instances(lib):
+    """The cases above must keep exercising every instance the launchers can pick (read from the published plan): a case set that
+    stops doing so fails here.  More than MB_R2 row blocks (two-level fold) is also required of the device cases."""
+    tab = ml.layer_table(lib)
+    seen = set(_child("plan", BIG_DEVICE, 256)["coverage"])
+    assert "pw_fwd tile 32 materialised producer" in seen and "pw_dgrad tile 32 without ss_in" in seen, seen
+    for B, M, T, C, *_ in LAYERWISE:
+        seen |= ml.coverage(tab, ml.workspace_map(lib, B, M, T, C))
+    assert (ml.REQUIRED | {"two-level arrival"}) <= seen, sorted((ml.REQUIRED | {"two-level arrival"}) - seen)
+
+
+def test_workspace_map_refuses_what_the_plan_refuses(lib):
+    d = ml.HowlMbWsLayer()
+    with pytest.raises(HowlHipError, match=r"howl_mobilenet_workspace_layer: batch too large for the stem kernels"):
+        lib.call("howl_mobilenet_workspace_layer", 512, 80, 20000, 5, 0, ctypes.byref(d))
+    with pytest.raises(HowlHipError, match=r"howl_mobilenet_workspace_layer: bad shape"):
+        lib.call("howl_mobilenet_workspace_layer", 4, 40, 0, 5, 0, ctypes.byref(d))
+    with pytest.raises(HowlHipError, match=r"howl_mobilenet_workspace_layer: index out of range"):
+        lib.call("howl_mobilenet_workspace_layer", 4, 40, 41, 5, 54, ctypes.byref(d))
+    wsl = ml.workspace_map(lib, 4, 40, 41, 5)
+    assert 4 * wsl[-1].total_floats + 256 == lib.cdll.howl_mobilenet_workspace_bytes(4, 40, 41, 5)
+    offs = sorted(o for w in wsl[:-1] for o in (w.z, w.g, w.y, w.ss, w.bc) if o >= 0)
+    assert len(set(offs)) == len(offs) and offs[-1] < wsl[-1].dz1 < wsl[-1].pooled < wsl[-1].pooled_d < wsl[-1].total_floats
+
+
+def test_layerwise_comparison_rules():
+    """The comparison itself: a decided element must match its own reference; an undecided one may match the other side, within
+    the same bound and no further; NaN never passes."""
+    def run(got, ref, bound, alt=None, und=None):
+        c = object.__new__(ml.Check)
+        c.ratios, c.fails = {}, []
+        t = lambda v: torch.tensor(v, dtype=torch.float64)
+        c.cmp("x", "here", t(got), t(ref), t(bound), alt=None if alt is None else t(alt),
+              und=None if und is None else torch.tensor(und), layout="c")
+        return c.fails, c.ratios["x"]
+    assert run([1.0, 2.0], [1.0, 2.0 + 1e-7], [0.0, 2e-7]) == ([], pytest.approx(0.5))
+    assert len(run([1.0, 2.0], [1.0 + 1e-9, 2.0], [0.0, 1e-7])[0]) == 1            # a zero bound means exactly equal
+    assert len(run([float("nan")], [0.0], [1.0])[0]) == 1
+    # masked reference 0, unmasked 3: the kernel's 3 passes only where the element is undecided
+    assert run([3.0], [0.0], [1e-6], alt=[3.0], und=[True])[0] == []
+    assert len(run([3.0], [0.0], [1e-6], alt=[3.0], und=[False])[0]) == 1
+    assert len(run([2.9], [0.0], [1e-6], alt=[3.0], und=[True])[0]) == 1

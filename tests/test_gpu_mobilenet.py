@@ -3,6 +3,7 @@
 import pytest
 import torch
 
+import mb_layerwise as ml
 from gpu_util import DEV, maxerr
 from mb_util import check_grads, oracle_step
 from oracle import frontend as ofe
@@ -258,3 +259,28 @@ def test_config5_at_full_size_with_device_collate():
     assert torch.isfinite(flat).all() and loss1 == loss1
     _, (audio2, _, logits2, _), flat2, _ = run()
     assert torch.equal(audio2, audio) and torch.equal(logits2, logits) and torch.equal(flat2, flat)
+
+
+# ---- layer-local float64 checks (tests/mb_layerwise.py) through the raw C ABI on device buffers --------------------------------
+# (B, M, T, labels, dropout, layout of x).  (96, 40, 101): multi-tile blocks, two-level arrival, both tile sizes side by side;
+# the last case passes x as (B, T, M) frames (st = M, sm = 1, slack between utterances).  All float64 work is on the CPU.
+LAYERWISE = [(7, 40, 57, 3, True, "bmt"), (9, 80, 61, 35, False, "bmt"), (96, 40, 101, 12, True, "bmt"), (6, 40, 45, 5, True, "btm")]
+
+
+@pytest.mark.parametrize("B,M,T,C,dropout,layout", LAYERWISE)
+def test_every_layer_vs_float64(B, M, T, C, dropout, layout):
+    """Every layer's forward and backward, each from the kernels' own neighbouring tensors, against float64 (see mb_layerwise);
+    the smallest case also checks the eval-mode forward."""
+    from howl_amd import lib
+    ml.run_case(lib.get(), ml.DevMem(), B, M, T, C, dropout, layout, eval_too=B == 7)
+
+
+def test_layerwise_cases_cover_the_kernel_instances():
+    """On this device the cases above must exercise every instance the launchers can pick, the two-level fold included."""
+    from howl_amd import lib
+    lb = lib.get()
+    tab, seen = ml.layer_table(lb), set()
+    for B, M, T, C, *_ in LAYERWISE:
+        seen |= ml.coverage(tab, ml.workspace_map(lb, B, M, T, C))
+    need = ml.REQUIRED | {"two-level arrival"}
+    assert need <= seen, sorted(need - seen)
