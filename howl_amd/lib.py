@@ -166,6 +166,14 @@ STREAM_SIGNATURES = {
 }
 STREAM_SIZE_FUNCS = {"howl_res8_stream_supported": [c_int, c_int, c_int], "howl_res8_stream_state_bytes": [c_int]}
 
+# The streaming seq-lstm / lstm entry points of ``include/howl_hip_lstm_stream.h`` (their own tables for the same reason:
+# ``tests/test_emu_lstm_stream.py`` checks them against that header)
+LSTM_STREAM_SIGNATURES = {
+    "howl_lstm_stream_chunks": [POINTER(HowlLstmParams), POINTER(HowlHeadParams), P, c_long, c_int, c_int, P, P, P, c_int, c_float, P,
+                                P, P, c_int, c_int, P, P, c_long, STREAM],
+}
+LSTM_STREAM_SIZE_FUNCS = {"howl_lstm_stream_supported": [c_int, c_int, c_int]}
+
 
 class HowlHipError(RuntimeError):
     pass
@@ -182,11 +190,11 @@ class Library:
         self.cdll = ctypes.CDLL(str(path))
         self.cdll.howl_last_error.restype = c_char_p
         self.cdll.howl_last_error.argtypes = []
-        for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES}.items():
+        for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES, **LSTM_STREAM_SIGNATURES}.items():
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = c_int
             fn.argtypes = argtypes
-        for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS}.items():
+        for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS, **LSTM_STREAM_SIZE_FUNCS}.items():
             fn = getattr(self.cdll, name)
             fn.restype = c_size_t
             fn.argtypes = argtypes

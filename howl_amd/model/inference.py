@@ -22,12 +22,15 @@ from howl_amd.utils import audio_utils
 from .base import RegisteredModel
 from .cnn import Res8
 from .decision import ProbabilitySmoother, SequenceMatcher
+from .rnn import SequentialLstm, SimpleLstm
 
 __all__ = ["FrameInferenceEngine", "InferenceEngine"]
 
 
 class InferenceEngine:
     """Sequential-model engine: one forward over the whole clip, then the frame-by-frame decision logic on the host."""
+
+    MAX_CLIPS_PER_LAUNCH = 8192      # infer_many: clips per streaming launch
 
     def __init__(self, model: RegisteredModel, zmuv_transform: ZmuvTransform, context: InferenceContext,
                  time_provider=time.time):
@@ -58,6 +61,10 @@ class InferenceEngine:
         self._matcher = SequenceMatcher(self.sequence, self.inference_window_ms, self.tolerance_window_ms)
         self.curr_time = 0
         self.label_history = []
+        # infer as ONE launch (LstmStreamSession) instead of the frontend + LSTM + head + softmax chain: off unless asked for
+        self.fused_chunks = os.environ.get("HOWL_STREAM_FUSED") == "1"
+        self._chunk_session = None
+        self.clip_histories = []      # infer_many: each clip's label_history
         self.reset()
 
     # the reference exposes both histories as plain attributes; pred_history lives in the smoother
@@ -104,14 +111,18 @@ class InferenceEngine:
         prediction = (prediction * self.inference_weights).astype(prediction.dtype, copy=False)
         return prediction / prediction.sum()
 
-    @torch.no_grad()
-    def infer(self, audio_data: torch.Tensor) -> bool:
-        """Whole clip as one batch through a sequential model (``inference.py:179-211``)."""
-        delta_ms = int(audio_data.size(-1) / self.sample_rate * 1000)
-        self.std = self.std.to(audio_data.device)
-        transformed = self.std.log_mel_for_model(audio_data.unsqueeze(0), self.zmuv)
-        predictions = self.model(transformed, lengths=None)
-        predictions = F.softmax(predictions, -1).squeeze(1).cpu().numpy()   # one device->host copy for all frames
+    def _lstm_session(self, kind, n_samples: int):
+        """The streaming session for chunks of up to ``n_samples`` samples, or None when it does not apply (another model, training
+        mode, a length outside the kernel's range): the caller then takes the launch chain."""
+        if not isinstance(self.model, kind) or self.model.training:
+            return None
+        s = self._chunk_session
+        if s is None or s.model is not self.model or s.std is not self.std or s.zmuv is not self.zmuv:
+            s = self._chunk_session = self.model.stream_session(self.std, self.zmuv)
+        return s if s.supported(n_samples) else None
+
+    def _run_frames(self, predictions: np.ndarray, delta_ms) -> bool:
+        """The frame-by-frame decision logic of ``infer`` on the (frames, C) probabilities of one chunk."""
         sequence_present = False
         delta_ms /= len(predictions)
         for prediction in predictions:
@@ -125,6 +136,63 @@ class InferenceEngine:
                 break
         return sequence_present
 
+    @torch.no_grad()
+    def infer(self, audio_data: torch.Tensor) -> bool:
+        """Whole clip as one batch through a sequential model (``inference.py:179-211``)."""
+        delta_ms = int(audio_data.size(-1) / self.sample_rate * 1000)
+        self.std = self.std.to(audio_data.device)
+        session = None
+        if self.fused_chunks and audio_data.dim() == 1 and audio_data.dtype == torch.float32:
+            session = self._lstm_session(SequentialLstm, audio_data.size(-1))
+        if session is not None:      # one launch, one host copy; the carried state read and assigned as SequentialLstm.forward does
+            streaming = self.model.is_streaming
+            probs, state = session.probabilities(audio_data.reshape(1, -1), state=self.model.streaming_state if streaming else None,
+                                                 return_state=streaming)
+            if streaming:
+                self.model.streaming_state = state
+            return self._run_frames(probs[0].cpu().numpy(), delta_ms)
+        transformed = self.std.log_mel_for_model(audio_data.unsqueeze(0), self.zmuv)
+        predictions = self.model(transformed, lengths=None)
+        predictions = F.softmax(predictions, -1).squeeze(1).cpu().numpy()   # one device->host copy for all frames
+        return self._run_frames(predictions, delta_ms)
+
+    @torch.no_grad()
+    def infer_many(self, clips) -> list:
+        """``[reset(); infer(clip) for clip in clips]``.  With ``fused_chunks`` on and every clip inside the streaming kernel's range:
+        the ragged clips padded into one (N, L_max) buffer and scored by ONE launch (each from a zero state, at most
+        ``MAX_CLIPS_PER_LAUNCH`` per launch) with one host copy, then the decision logic replayed per clip on the host exactly as
+        ``infer`` runs it.  Otherwise the plain loop.  Leaves the engine reset; ``clip_histories`` keeps each clip's
+        ``label_history``."""
+        clips = list(clips)
+        self.clip_histories = []
+        session = None
+        if self.fused_chunks and clips and all(c.dim() == 1 and c.dtype == torch.float32 for c in clips):
+            self.std = self.std.to(clips[0].device)
+            session = self._lstm_session(SequentialLstm, max(c.size(-1) for c in clips))
+            if session is not None and not session.supported(min(c.size(-1) for c in clips)):
+                session = None
+        res = []
+        if session is None:
+            for clip in clips:
+                self.reset()
+                res.append(bool(self.infer(clip)))
+                self.clip_histories.append(list(self.label_history))
+            self.reset()
+            return res
+        for lo in range(0, len(clips), self.MAX_CLIPS_PER_LAUNCH):
+            group = clips[lo:lo + self.MAX_CLIPS_PER_LAUNCH]
+            sizes = [c.size(-1) for c in group]
+            pcm = torch.nn.utils.rnn.pad_sequence(group, batch_first=True)
+            n_samples = torch.tensor(sizes, dtype=torch.int64).to(pcm.device)
+            probs, _ = session.probabilities(pcm, n_samples=n_samples, return_state=False)
+            probs = probs.cpu().numpy()
+            for n, row in zip(sizes, probs):
+                self.reset()
+                res.append(self._run_frames(row[:1 + n // 200], int(n / self.sample_rate * 1000)))
+                self.clip_histories.append(list(self.label_history))
+        self.reset()
+        return res
+
 
 class FrameInferenceEngine(InferenceEngine):
     def __init__(self, max_window_size_ms: int, eval_stride_size_ms: int, *args):
@@ -133,6 +201,7 @@ class FrameInferenceEngine(InferenceEngine):
         # ingest_frame as ONE launch (Res8StreamSession) instead of the frontend + res8 + softmax chain: off unless asked for
         self.fused_windows = os.environ.get("HOWL_STREAM_FUSED") == "1"
         self._stream_session = None
+        self._frames_cache = {}
 
     def _stateless(self) -> bool:
         return not self.model.is_streaming or type(self.model).streaming_state is RegisteredModel.streaming_state
@@ -254,10 +323,23 @@ class FrameInferenceEngine(InferenceEngine):
                 break
         return sequence_present
 
+    def _window_frames(self, frame):
+        """``compute_lengths`` of this window as a (1,) int64 device tensor, or None below one frame.  It depends on the window's size
+        alone: computed on the host and copied once per (size, device), not once per window."""
+        key = (frame.size(-1), frame.device)
+        if key not in self._frames_cache:
+            n = int(self.std.compute_lengths(torch.tensor([frame.size(-1)]))[0])
+            self._frames_cache[key] = torch.tensor([n], dtype=torch.int64).to(frame.device) if n >= 1 else None
+        return self._frames_cache[key]
+
     def _fused_session(self, frame):
         """The streaming session for this window, or None when it does not apply (another model, training mode, a window outside
         the kernel's range): ``ingest_frame`` then takes the launch chain."""
-        if not isinstance(self.model, Res8) or self.model.training or frame.dim() != 1 or frame.dtype != torch.float32:
+        if frame.dim() != 1 or frame.dtype != torch.float32:
+            return None
+        if isinstance(self.model, SimpleLstm):      # (a window with no whole 512-sample frame has compute_lengths < 1: the chain's business)
+            return self._lstm_session(SimpleLstm, frame.size(-1)) if self._window_frames(frame) is not None else None
+        if not isinstance(self.model, Res8) or self.model.training:
             return None
         s = self._stream_session
         if s is None or s.model is not self.model or s.std is not self.std or s.zmuv is not self.zmuv:
@@ -269,6 +351,10 @@ class FrameInferenceEngine(InferenceEngine):
         """One window, as the live client feeds it (``inference.py:247-267``)."""
         self.std = self.std.to(frame.device)
         session = self._fused_session(frame) if self.fused_windows else None
+        if session is not None and isinstance(self.model, SimpleLstm):      # one launch, one host copy; frames as compute_lengths
+            frames = self._window_frames(frame)
+            prediction = session.probabilities(frame.reshape(1, -1), frames=frames)[0][0].cpu().numpy()
+            return self._append_probability_frame(self._weighted(prediction), curr_time=curr_time)
         if session is not None:      # one launch, one host copy
             prediction = session.probabilities(frame.reshape(1, -1))[0].cpu().numpy()
             return self._append_probability_frame(self._weighted(prediction), curr_time=curr_time)

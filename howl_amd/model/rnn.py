@@ -17,7 +17,7 @@ from howl_amd.settings import _EnvSettings
 
 from .base import RegisteredModel
 
-__all__ = ["LstmConfig", "SequentialLstm", "SimpleLstm"]
+__all__ = ["LstmConfig", "LstmStreamSession", "SequentialLstm", "SimpleLstm"]
 
 HID = 128
 
@@ -238,7 +238,71 @@ class _HeadFunction(torch.autograd.Function):
         return (dx,) + tuple(grads)
 
 
+class LstmStreamSession:
+    """Streaming seq-lstm / lstm: ``probabilities(pcm, ...)`` takes N independent raw PCM chunks to their class probabilities in ONE
+    kernel launch (``howl_lstm_stream_chunks``: log-mel + ZMUV, the recurrence, the head and the softmax, four streams per
+    workgroup; no gate / cell / hidden-sequence stores, nothing of the head through HBM).  The weights are read in place on every
+    call: nothing is prepared, nothing can go stale.  Eval mode only, standard filterbank only.
+
+    ``seq-lstm``: probs (N, 1 + L_max // 200, C), rows behind a stream's last frame zero, and the carried state as the pair of
+    (1, N, 128) tensors ``model.streaming_state`` holds.  ``lstm``: the head on the final hidden state only, probs (N, C), no state
+    (``SimpleLstm`` is stateless between calls, rnn.py:89-90)."""
+
+    def __init__(self, model, std, zmuv):
+        self.model, self.std, self.zmuv = model, std, zmuv
+        self.last_only = isinstance(model, SimpleLstm)
+        self._own = None      # the state pair this session returned last: handed back, it is advanced in place
+
+    def supported(self, n_samples: int) -> bool:
+        """Chunks of up to ``n_samples`` samples are inside the kernel's range (40 mel bins, 400 samples .. 8192 frames, <= 64 labels)
+        and the frontend would not draw a VTLP filterbank for them."""
+        vtlp = self.std.augment_params[0].enabled and self.std.training
+        return not vtlp and ops.lstm_stream_supported(n_samples, self.std.n_mels, self.model.num_labels)
+
+    @torch.no_grad()
+    def probabilities(self, pcm: torch.Tensor, n_samples: torch.Tensor = None, frames: torch.Tensor = None, state=None,
+                      return_state: bool = True, logits: torch.Tensor = None):
+        """pcm: (N, L_max) fp32 on the device, unit sample stride; ``n_samples`` (N) int64 on the device, the samples of each chunk
+        (None: L_max for all); ``frames`` (N) int64 on the device, the frames to run (None: all ``1 + n_samples // 200``); ``state``:
+        the (h, c) pair to start from, (1, N, 128) each, None = zeros.  -> (probs, state).  The returned state tensors belong to the
+        session: handed back as ``state`` of the next call they are advanced in place (no copy); any other pair is copied first.
+        ``return_state=False`` with ``state=None``: no state is carried at all (a pass over whole clips)."""
+        if self.model.training:
+            raise RuntimeError("LstmStreamSession runs the inference path (no saved activations): call model.eval() first")
+        if pcm.dim() != 2 or not self.supported(pcm.size(1)):
+            raise ValueError(f"LstmStreamSession: chunks of shape {tuple(pcm.shape)} are outside the streaming kernel's range "
+                             f"(see supported()); use the model's forward")
+        if self.std.augment_params[0].enabled:
+            self.std.rand.random()      # the frontend's draw happens on every call, eval mode included: keep the stream's position
+        N = pcm.size(0)
+        h = c = None
+        if not self.last_only and (state is not None or return_state):
+            if state is not None and (tuple(state[0].shape) != (1, N, HID) or tuple(state[1].shape) != (1, N, HID)):
+                raise RuntimeError(f"Expected hidden size (1, {N}, {HID}), got {tuple(state[0].shape)}")     # as nn.LSTM does
+            own = self._own
+            if state is not None and own is not None and state[0] is own[0] and state[1] is own[1]:
+                h, c = own
+            else:
+                hc = torch.zeros((2, 1, N, HID), dtype=torch.float32, device=pcm.device)
+                if state is not None:
+                    hc[0].copy_(state[0])
+                    hc[1].copy_(state[1])
+                h, c = hc[0], hc[1]
+        l, d = self.model.lstm, self.model.dnn
+        lstm_prm = _lib.HowlLstmParams(_vp(l.weight_ih_l0), _vp(l.weight_hh_l0), _vp(l.bias_ih_l0), _vp(l.bias_hh_l0))
+        head_prm = _lib.HowlHeadParams(_vp(d[0].weight), _vp(d[0].bias), _vp(d[2].weight), _vp(d[2].bias))
+        pair = self.zmuv.pair() if self.zmuv is not None else None
+        probs = ops.lstm_stream_chunks(lstm_prm, head_prm, pcm, self.std._standard_fb(), self.std.n_mels, pair, self.model.num_labels,
+                                       n_samples=n_samples, frames=frames, h=h, c=c, last_only=self.last_only, logits=logits)
+        self._own = (h, c) if h is not None else None
+        return probs, self._own
+
+
 class _LstmBase(RegisteredModel):
+    def stream_session(self, std, zmuv) -> LstmStreamSession:
+        """One-launch inference from raw PCM for this model (see ``LstmStreamSession``)."""
+        return LstmStreamSession(self, std, zmuv)
+
     def __init__(self, num_labels: int, config: LstmConfig = None):
         super().__init__(num_labels)
         config = config or LstmConfig()

@@ -293,3 +293,32 @@ def res8_stream_windows(state, pcm, fbp, n_mels, zmuv_pair, n_labels, probs=None
                     int(n_mels), log_eps, _p(zmuv_pair, allow_none=True), int(n_labels), _p(probs), _p(logits, allow_none=True),
                     _stream())
     return probs
+
+
+# ---- streaming seq-lstm / lstm (include/howl_hip_lstm_stream.h): one launch from N PCM chunks to their frame probabilities --------
+
+def lstm_stream_supported(L_max: int, n_mels: int, n_labels: int) -> bool:
+    return bool(_lib.get().cdll.howl_lstm_stream_supported(int(L_max), int(n_mels), int(n_labels)))
+
+
+def lstm_stream_chunks(lstm_prm, head_prm, pcm, fbp, n_mels, zmuv_pair, n_labels, n_samples=None, frames=None, h=None, c=None,
+                       last_only=False, probs=None, logits=None, log_eps: float = 1e-7):
+    """(N, L_max) PCM chunks (unit sample stride, any row stride) -> probabilities in one launch: (N, 1 + L_max // 200, C), or (N, C)
+    with ``last_only``.  ``lstm_prm`` / ``head_prm``: ``HowlLstmParams`` / ``HowlHeadParams`` records; ``n_samples`` / ``frames``: (N)
+    int64 on the device or None; ``h`` / ``c``: (N, 128) start state, overwritten with the carried state (both or neither);
+    ``logits``, when given, receives the pre-softmax scores in the layout of ``probs``."""
+    if pcm.dim() != 2:
+        raise ValueError("pcm must be (N, L_max)")
+    if pcm.stride(1) != 1:
+        pcm = pcm.contiguous()
+    if not on_device(pcm) or pcm.dtype != torch.float32:
+        _p(pcm)
+    N, L = pcm.shape
+    if probs is None:
+        shape = (N, n_labels) if last_only else (N, num_frames(L), n_labels)
+        probs = torch.empty(shape, dtype=torch.float32, device=pcm.device)
+    _lib.get().call("howl_lstm_stream_chunks", ctypes.byref(lstm_prm), ctypes.byref(head_prm), ctypes.c_void_p(pcm.data_ptr()),
+                    pcm.stride(0) if N > 1 else L, N, L, _p(n_samples, torch.int64, allow_none=True), _p(frames, torch.int64, allow_none=True),
+                    _p(fbp), int(n_mels), log_eps, _p(zmuv_pair, allow_none=True), _p(h, allow_none=True), _p(c, allow_none=True),
+                    int(n_labels), 1 if last_only else 0, _p(probs), _p(logits, allow_none=True), probs.stride(0), _stream())
+    return probs

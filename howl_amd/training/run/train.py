@@ -177,8 +177,8 @@ def main(argv=None):
             engine = InferenceEngine(model, zmuv_transform, ctx)
         hits = 0
         mine = ids[rank::world]            # clips dealt round-robin to the ranks, detections summed
-        if use_frame:                      # all windows of 64 clips at a time in one batch (FrameInferenceEngine.infer_many)
-            for lo in range(0, len(mine), 64):
+        if use_frame or engine.fused_chunks:      # 64 clips per call: all of their windows in one batch (FrameInferenceEngine.infer_many),
+            for lo in range(0, len(mine), 64):    # or the ragged whole clips in one streaming launch (InferenceEngine.infer_many)
                 model.streaming_state = None
                 hits += sum(int(h) for h in engine.infer_many([bank.clip(i) for i in mine[lo:lo + 64]]))
             mine = []

@@ -5,7 +5,12 @@ windows at a 63 ms stride over the 10 s synthetic clips that ``bench.py --config
 five repeats of 1000 windows each, the MEDIAN of each repeat; eager (``fused_windows = False``) and fused alternate repeat by repeat,
 in one process, on one card.  In addition, for N = 64 and N = 256 windows per launch: ``Res8StreamSession.probabilities`` alone
 between two HIP events beside ``engine.window_probabilities`` on the same windows (wall time, host copy included: what that call
-is).  Prints one JSON line.  ``--windows`` / ``--repeats`` shorten a run (a profiler pass); the protocol is the default."""
+is).  Prints one JSON line.  ``--windows`` / ``--repeats`` shorten a run (a profiler pass); the protocol is the default.
+
+``--model seq-lstm``: the same protocol for ``InferenceEngine.infer`` (LstmStreamSession): (a) 8000-sample chunks (what the live
+client feeds), (b) 16000-sample chunks, both with the state carried from call to call; (c) ``infer_many`` on 64 clips of 1 - 3 s
+against the clip-by-clip ``[reset(); infer(clip)]`` loop (per CALL of 64 clips; ``--windows`` / 20 calls per repeat); and the
+kernel alone between two HIP events for each of the three shapes."""
 import argparse
 import json
 import os
@@ -26,7 +31,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--fused-only", action="store_true", help="skip the eager path (a kernel-trace pass over the one launch)")
+    ap.add_argument("--eager-only", action="store_true", help="seq-lstm: skip the fused path (a kernel-trace pass over the launch chain)")
+    ap.add_argument("--model", choices=["res8", "seq-lstm"], default="res8")
     args = ap.parse_args()
+    if args.model == "seq-lstm":
+        return main_seq_lstm(args)
     import torch
     from howl_amd.context import InferenceContext
     from howl_amd.data.transform.operator import ZmuvTransform
@@ -108,6 +117,104 @@ def main():
         "fused_us_medians": [round(v, 2) for v in fused_m], "eager_us_medians": [round(v, 2) for v in eager_m],
         "requirement_max_fused_below_min_eager": (max(fused_m) < min(eager_m)) if eager_m else None,
         "many_windows": many}), flush=True)
+
+
+def main_seq_lstm(args):
+    import numpy as np
+    import torch
+    from howl_amd.context import InferenceContext
+    from howl_amd.data.transform.operator import ZmuvTransform
+    from howl_amd.data.transform.transform import StandardAudioTransform
+    from howl_amd.model import RegisteredModel
+    from howl_amd.model.inference import InferenceEngine
+    from howl_amd.utils.synth import synthetic_pcm
+    dev = torch.device("cuda:0")
+    ctx = InferenceContext(["hey", "fire", "fox"], token_type="word", use_blank=True)
+    torch.manual_seed(2024)
+    model = RegisteredModel.find_registered_class("seq-lstm")(ctx.num_labels).to(dev).eval().streaming()
+    std = StandardAudioTransform().to(dev).eval()
+    zmuv = ZmuvTransform().to(dev)
+    clips = synthetic_pcm(8, 160000, seed=77).to(dev)                  # 8 clips of 10 s
+    zmuv.update(std(clips[:1, :16000]))
+    engine = InferenceEngine(model, zmuv, ctx)
+    engine.sequence = [0, 1, 2, 0, 1, 2, 0, 1, 2]                      # never present: every call walks all of its frames
+    paths = [True] if args.fused_only else ([False] if args.eager_only else [False, True])
+
+    def chunks_of(size):
+        return [clip[s:s + size] for clip in clips for s in range(0, 160000 - size + 1, size)]
+
+    def run_chunks(fused, chunks, n, first):
+        engine.fused_chunks = fused
+        engine.reset()
+        times = []
+        for i in range(n):
+            chunk = chunks[(first + i) % len(chunks)]
+            t0 = time.perf_counter()
+            engine.infer(chunk)
+            times.append(time.perf_counter() - t0)
+        return times
+
+    rng = np.random.default_rng(7)
+    sizes = [int(v) for v in rng.integers(16000, 48001, 64)]
+    many = [clips[i % 8, :n].contiguous() for i, n in enumerate(sizes)]
+
+    def run_many(fused, n):
+        engine.fused_chunks = fused
+        times = []
+        for i in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if fused:
+                engine.infer_many(many)
+            else:
+                for clip in many:
+                    engine.reset()
+                    engine.infer(clip)
+            times.append(time.perf_counter() - t0)
+        return times
+
+    out = {"metric": "InferenceEngine.infer / infer_many wall time per call, us (seq-lstm, host copy included; median of each repeat)",
+           "calls_per_repeat": args.windows, "warmup_calls": args.warmup}
+    for name, size in (("a_8000_sample_chunks", 8000), ("b_16000_sample_chunks", 16000)):
+        chunks = chunks_of(size)
+        for fused in paths:
+            run_chunks(fused, chunks, args.warmup, 0)
+        med = {True: [], False: []}
+        for r in range(args.repeats):
+            for fused in paths:
+                med[fused].append(statistics.median(run_chunks(fused, chunks, args.windows, r * args.windows)) * 1e6)
+        out[name] = {"fused_us_medians": [round(v, 2) for v in med[True]], "eager_us_medians": [round(v, 2) for v in med[False]]}
+    n_many = max(2, args.windows // 20)
+    for fused in paths:
+        run_many(fused, max(1, args.warmup // 20))
+    med = {True: [], False: []}
+    for r in range(args.repeats):
+        for fused in paths:
+            med[fused].append(statistics.median(run_many(fused, n_many)) * 1e6)
+    out["c_infer_many_64_clips_1_to_3_s"] = {"calls_per_repeat": n_many, "frames_per_call": sum(1 + n // 200 for n in sizes),
+                                            "fused_us_medians": [round(v, 2) for v in med[True]],
+                                            "eager_loop_us_medians": [round(v, 2) for v in med[False]]}
+    if args.eager_only:
+        print(json.dumps(out), flush=True)
+        return
+    # the kernel alone, between two HIP events
+    session = model.stream_session(std, zmuv)
+    pad = torch.nn.utils.rnn.pad_sequence(many, batch_first=True)
+    ns = torch.tensor(sizes, dtype=torch.int64, device=dev)
+    kernel = {}
+    for name, pcm, n_samples in (("a_N1_8000", clips[:1, :8000], None), ("b_N1_16000", clips[:1, :16000], None), ("c_N64_1_to_3_s", pad, ns)):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        us = []
+        for i in range(60):
+            e0.record()
+            session.probabilities(pcm, n_samples=n_samples, return_state=False)
+            e1.record()
+            e1.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        kernel[name] = round(statistics.median(us[10:]), 2)
+    out["launch_us_median_between_hip_events"] = kernel
+    torch.cuda.synchronize()
+    print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":
