@@ -1272,72 +1272,286 @@ __global__ __launch_bounds__(SH_THREADS) void seq_head_ctc_kernel(SeqHeadArgs a)
     }
 }
 
+// ---- host side.  One plan per call: HeadPlan / LstmPlan hold what the host derives from a problem's shape, its operands'
+// alignment, the CU count and the environment switches (read per call: the tests flip them inside one process).  Only the two
+// builders read those; size queries, refusals and launches read the plan, and an entry point returns every refusal (null
+// pointer, then shape, then workspace) before its first launch. ----
+bool env_is(const char* name, char c) { return getenv(name) != nullptr && getenv(name)[0] == c; }
+bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+int refuse_workspace(const char* who) {
+    howl_set_error("%s: workspace too small", who);
+    return HOWL_E_WORKSPACE;
+}
+// a kernel instance's dynamic-LDS limit, raised once per device (one table per instance); refused: HOWL_CHECK_LAUNCH reports it
+template <auto Kernel>
+void raise_lds_limit(size_t lds, const char* who) {
+    static thread_local size_t granted[16] = {};
+    howl_raise_lds(reinterpret_cast<const void*>(Kernel), lds, granted, who);
+}
+// f(integral_constant<int, NO>) for n_out = NO in 1..8: the instances of the head's four kernel templates
+template <int NO = 1, class F>
+void for_n_out(int n_out, F&& f) {
+    if constexpr (NO <= 8) n_out == NO ? f(std::integral_constant<int, NO>{}) : for_n_out<NO + 1>(n_out, f);
+}
+
 // workspace of one Linear layer's backward on the GEMM path, in floats: split-K slabs of the weight gradient (<= 128) + 256 slabs
 // of n_out for the bias column sums
 size_t linear_ws_floats(int n_out, int n_in) { return (size_t)HEAD_W1_SPLITS * n_out * (n_in > 1 ? n_in : 1) + (size_t)256 * n_out + 64; }
 
-bool head_is_thin(int n_hid, int n_out) { return n_out >= 1 && n_out <= 8 && n_hid <= HEAD_MAX_HID && (n_hid & 3) == 0; }
-
-// How (and whether) seq_head_ctc_kernel covers a batch: U utterances per group, groups, workgroups (= slabs of partial sums)
-struct SeqHeadGeom {
-    int U, ngroups, blocks;
+// How the backward of the Linear - ReLU - Linear head over `rows` rows (utterances of rows_inner rows) runs.  HEAD_FOLD:
+// howl_seq_head_ctc ran the rows (dz1, dx and one slab of partial sums per workgroup are in place), only the folds are left;
+// HEAD_ROWS: many rows, second layer's backward + ReLU mask + dx = dz1 W1 in one launch; HEAD_THIN: n_out <= 8 on the vector
+// kernel; HEAD_GEMM: every other shape, the second layer by the GEMM path with its own folds
+enum HeadBwdPath { HEAD_FOLD, HEAD_ROWS, HEAD_THIN, HEAD_GEMM };
+struct HeadBwdOperands { const float *y1, *dy2, *dz1, *dx, *w2; };      // what the choice of the path looks at besides the shape
+struct HeadPlan {
+    bool thin;           // n_out <= 8: the second layer on the vector kernels (forward: out_blocks workgroups of head_out_kernel)
+    int out_blocks;
+    // whether seq_head_ctc_kernel covers the rows: U utterances per group, groups, workgroups (= slabs), dynamic LDS
+    bool seq;
+    int U, ngroups, seq_blocks;
     size_t lds_bytes;
+    // the path, its workgroups, head_thin_bwd_kernel's rows per workgroup; a thin path's workgroup leaves one slab of `slab`
+    // floats: dW2 (n_out, n_hid), db1 (n_hid), db2 (n_out)
+    HeadBwdPath path;
+    int blocks, rpb;
+    long slab;
+    // workspace: [first layer: up to 128 split-K slabs of n_hid x n_in] [thin paths: HEAD_BWD_BLOCKS slabs]; HEAD_GEMM: b1's column
+    // sums behind the first layer's slabs, then the second layer's slabs and b2's column sums
+    float *first, *thin_slabs, *scratch_b1, *ws2, *scratch_b2;
+    size_t bytes;
 };
-bool seq_head_geometry(int B, int T, int n_in, int n_hid, int n_out, int max_target, SeqHeadGeom* g) {
-    if (n_in != HB_IN || n_hid != HB_HID || n_out < 1 || n_out > 8 || B < 1 || T < 1 || T > CTC_CHUNK) return false;
-    if (2 * max_target + 1 > SH_RPC) return false;                       // the CTC rows hold <= 17 states
-    if ((long)B * T < rowgemm_min_rows() || (long)B * T >= (1L << 20)) return false;     // few rows: the tile kernels keep more CUs busy
-    const char* e = getenv("HOWL_SEQ_HEAD_FUSED");
-    if (e != nullptr && e[0] == '0') return false;
-    constexpr size_t LDS_MAX = 160 * 1024;
-    int U = 0;
-    for (int u = 2; u >= 1; --u)
-        if (seq_head_lds_floats(u, T, n_out) * sizeof(float) <= LDS_MAX) {
-            U = u;
-            break;
-        }
-    if (U == 0) return false;
-    g->U = U;
-    g->ngroups = (B + U - 1) / U;
-    g->blocks = std::min(std::min(g->ngroups, howl_num_cus()), HEAD_BWD_BLOCKS);
-    g->lds_bytes = seq_head_lds_floats(U, T, n_out) * sizeof(float);
-    return true;
+HeadPlan head_plan(long rows, int rows_inner, int n_in, int n_hid, int n_out, int max_target = 0, void* ws = nullptr,
+                   const HeadBwdOperands* o = nullptr) {
+    HeadPlan p{};
+    const int cus = howl_num_cus();
+    const bool thin = p.thin = n_out >= 1 && n_out <= 8 && n_hid <= HEAD_MAX_HID && (n_hid & 3) == 0;
+    // the row-streaming kernels: 128 -> 256 -> <= 8 and enough rows (fewer: the tile kernels keep more CUs busy) ...
+    const bool streams = thin && n_in == HB_IN && n_hid == HB_HID && rows >= rowgemm_min_rows() && rows < (1L << 20);
+    // ... in one launch with the CTC recursions: whole utterances of <= 128 frames and <= 17 CTC states, two or one per workgroup
+    if (streams && rows_inner >= 1 && rows_inner <= CTC_CHUNK && rows % rows_inner == 0 && 2 * max_target + 1 <= SH_RPC &&
+        !env_is("HOWL_SEQ_HEAD_FUSED", '0'))
+        for (int u = 2; u >= 1 && !p.seq; --u)
+            if (seq_head_lds_floats(u, rows_inner, n_out) * sizeof(float) <= 160 * 1024) {
+                p.seq = true;
+                p.U = u;
+                p.ngroups = ((int)(rows / rows_inner) + u - 1) / u;
+                p.seq_blocks = std::min(std::min(p.ngroups, cus), HEAD_BWD_BLOCKS);
+                p.lds_bytes = seq_head_lds_floats(u, rows_inner, n_out) * sizeof(float);
+            }
+    p.out_blocks = (int)std::min((rows + 15) / 16, 4L * cus);
+    p.slab = (long)(n_out + 1) * n_hid + n_out;
+    p.path = HEAD_GEMM;
+    if (o != nullptr && o->dy2 == nullptr) {
+        p.path = HEAD_FOLD;
+        p.blocks = p.seq_blocks;
+    } else if (o != nullptr && streams && o->dx != nullptr && al16(o->y1) && al16(o->dz1) && al16(o->dx) && al16(o->w2) &&
+               getenv("HOWL_GEMM_NO_ROWGEMM") == nullptr) {
+        p.path = HEAD_ROWS;
+        p.blocks = std::min(std::min((int)((rows + 15) / 16), cus), HEAD_BWD_BLOCKS);
+    } else if (thin) {
+        p.path = HEAD_THIN;
+        p.rpb = (int)((rows + HEAD_BWD_BLOCKS - 1) / HEAD_BWD_BLOCKS + 7) / 8 * 8;
+        p.blocks = (int)((rows + p.rpb - 1) / p.rpb);
+    }
+    const size_t first = (size_t)HEAD_W1_SPLITS * n_hid * n_in, thin_all = (size_t)HEAD_BWD_BLOCKS * (size_t)p.slab;
+    p.bytes = (std::max(first + thin_all, linear_ws_floats(n_hid, n_in) + linear_ws_floats(n_out, n_hid)) + 64) * sizeof(float);
+    if (ws != nullptr) {
+        p.first = static_cast<float*>(ws);
+        p.thin_slabs = p.scratch_b1 = p.first + first;
+        p.ws2 = p.first + linear_ws_floats(n_hid, n_in);
+        p.scratch_b2 = p.ws2 + (size_t)HEAD_W1_SPLITS * n_out * n_hid;
+    }
+    return p;
 }
 
-// Which recurrence pair runs: four sequences per workgroup (v_mfma 4x4x1_16b: 93 / 73 us per 38-step launch, one workgroup
-// per CU) while that leaves at most two rounds of workgroups, sixteen per workgroup (16x16x4: 213 / 198 us) beyond --
-// B <= 8 x CUs = 2048 on this part.  HOWL_LSTM_ROWS=4|16 forces one (tests exercise both).
-bool lstm_rows16(int B, int T) {
-    if ((size_t)B * (size_t)(T + 1) * G4 * sizeof(float) >= ((size_t)1 << 32)) return true;   // the 4-row kernels index bytes in 32 bits
-    const char* env = getenv("HOWL_LSTM_ROWS");
-    if (env != nullptr && env[0] == '1') return true;
-    if (env != nullptr && env[0] == '4') return false;
-    return B > 8 * howl_num_cus();
+constexpr size_t LSTM_FWD16_LDS = (size_t)(2 * 16 * HS + 2 * 16 * 6 * HID) * sizeof(float);      // lstm_fwd_kernel's dynamic LDS
+// How one LSTM problem (B sequences, T steps of which t_out run, M input features in rows of x_frames frames) runs
+enum HeadRide { RIDE_BEHIND, RIDE_LAUNCH, RIDE_LANE };
+struct LstmPlan {
+    char bad[96];      // why the problem is refused (the entry point puts its name in front), or empty
+    // which recurrence pair runs: four sequences per workgroup (v_mfma 4x4x1_16b) while that leaves at most two rounds of
+    // workgroups, sixteen (16x16x4) beyond B = 8 x CUs and where the 4-row kernels' 32-bit byte offsets end (HOWL_LSTM_ROWS=4|16)
+    bool rows16;
+    bool fuse_x;      // the four-sequence forward multiplies x_t W_ih^T itself (M = 40): no projection launch, gx unused
+    int xf, nrec, rows;      // frames per row of x; workgroups of a four-sequence recurrence; B * t_out
+    // forward: the next batch's frontend rides in the fused four-sequence recurrence's launch as nb more workgroups while that
+    // leaves half of the device idle (otherwise, and with HOWL_LSTM_RIDE_LOGMEL=0: behind it)
+    bool ride;
+    int nb;
+    // howl_seq_lstm_bwd: the head's first-layer weight gradient (dz1^T H) needs nothing the LSTM's backward produces: while the
+    // four-sequence recurrence leaves half of the device idle its blocks ride in that launch.  HOWL_LSTM_RIDE: "lane" = on the
+    // library's side lane instead (measured 9 us worse), "0" = behind the recurrence with the other weight gradients.
+    HeadRide head_ride;
+    bool fold_adamw;      // the optimiser step may ride in the slab fold (HOWL_NO_FOLD_ADAMW)
+    // rows (b, t < t_out) of dG, x and h_{t-1} for the weight-gradient reductions (steps t >= t_out never ran and their dG rows
+    // are never written)
+    RowMap rows_g, rows_x, rows_h;
+    // workspace: packed W_hh of the 16-row recurrences, forward and backward (64K floats each), their folded bias (512), split-K
+    // slabs of the W_hh (128 x 512 x 128) and W_ih gradients (128 x 512 x 96 at most), bias_slabs x 512 (one per workgroup of the
+    // four-sequence recurrence, or the column-sum kernel's 256): three slab regions, so that their sums can run as one launch
+    float *w_hh_f, *w_hh_b, *bsum, *slabs_hh, *slabs_ih, *slabs_b;
+    size_t bias_slabs, bytes;
+};
+LstmPlan lstm_plan(const HowlLstmParams* p, int B, int T, int M, int t_out, int x_frames, bool backward, void* ws = nullptr,
+                   const LogmelLaunch* next = nullptr) {
+    LstmPlan q{};
+    const int cus = howl_num_cus();
+    q.xf = x_frames > 0 ? x_frames : T;
+    if (!(B >= 1 && T >= 1 && M >= 1)) snprintf(q.bad, sizeof(q.bad), "bad shape");
+    else if (!(t_out >= 1 && t_out <= T)) snprintf(q.bad, sizeof(q.bad), "t_out=%d outside 1..T", t_out);
+    else if (q.xf < T) snprintf(q.bad, sizeof(q.bad), "x_frames=%d < T=%d", q.xf, T);
+    else if (backward && M > LSTM_MAX_IN)
+        snprintf(q.bad, sizeof(q.bad), "M=%d input features exceed the workspace layout (max %d)", M, LSTM_MAX_IN);
+    q.rows16 = (size_t)B * (size_t)(T + 1) * G4 * sizeof(float) >= ((size_t)1 << 32) || env_is("HOWL_LSTM_ROWS", '1') ||
+               (!env_is("HOWL_LSTM_ROWS", '4') && B > 8 * cus);
+    q.fuse_x = !q.rows16 && M == 40 && p != nullptr && al16(p->w_ih) && (size_t)B * (size_t)q.xf * M * sizeof(float) < ((size_t)1 << 32) &&
+               getenv("HOWL_LSTM_NO_FUSED_X") == nullptr;
+    q.nrec = (B + 3) / 4;
+    q.rows = B * t_out;
+    const bool idle_half = !q.rows16 && q.nrec <= cus / 2;
+    q.ride = next != nullptr && q.fuse_x && idle_half && next->M <= 4 * NG_BANDED && !env_is("HOWL_LSTM_RIDE_LOGMEL", '0');
+    q.nb = q.ride ? std::max(1, std::min(next->n_quads, cus - q.nrec)) : 0;
+    const char* hr = getenv("HOWL_LSTM_RIDE");
+    q.head_ride = !idle_half ? RIDE_BEHIND : (hr == nullptr || hr[0] == '1') ? RIDE_LAUNCH : hr[0] == 'l' ? RIDE_LANE : RIDE_BEHIND;
+    q.fold_adamw = getenv("HOWL_NO_FOLD_ADAMW") == nullptr;
+    const bool full = t_out == T;
+    q.rows_g = full ? lin(G4) : RowMap{t_out, (long)T * G4, G4};
+    q.rows_x = (full && q.xf == T) ? lin(M) : RowMap{t_out, (long)q.xf * M, M};
+    q.rows_h = RowMap{t_out, (long)(T + 1) * HID, HID};
+    size_t off = 0;
+    auto region = [&](size_t floats) {      // the layout, once: a size query (ws == nullptr) walks it for the total only
+        off += floats;
+        return ws != nullptr ? static_cast<float*>(ws) + (off - floats) : nullptr;
+    };
+    q.bias_slabs = std::max((size_t)(B + 3) / 4, (size_t)256);
+    q.w_hh_f = region(16 * 64 * 64);
+    q.w_hh_b = region(16 * 64 * 64);
+    q.bsum = region(G4);
+    q.slabs_hh = region((size_t)LSTM_WGRAD_SPLITS * G4 * HID);
+    q.slabs_ih = region((size_t)LSTM_WGRAD_SPLITS * G4 * LSTM_MAX_IN);
+    q.slabs_b = region(q.bias_slabs * G4);
+    q.bytes = off * sizeof(float) + 1024;
+    return q;
 }
+
+// One howl_lstm_bwd problem (alone, or the LSTM half of howl_seq_lstm_bwd): the call's arguments and its plan
+struct LstmBwd {
+    const HowlLstmParams* p;
+    const HowlLstmSaved* sv;
+    const HowlLstmGrads* g;
+    const long long* lengths;
+    const float *x, *c0, *dy, *dhT, *dcT;
+    int B, T, M;
+    void* ws;
+    size_t ws_bytes;
+    LstmPlan q;
+    int plan() {      // every refusal of the call
+        HOWL_REQUIRE(p && x && sv && g && ws, "howl_lstm_bwd: null pointer");
+        HOWL_REQUIRE(dy || dhT, "howl_lstm_bwd: no incoming gradient");
+        q = lstm_plan(p, B, T, M, sv->t_out, sv->x_frames, true, ws);
+        HOWL_REQUIRE(q.bad[0] == 0, "howl_lstm_bwd: %s", q.bad);
+        return ws_bytes < q.bytes ? refuse_workspace("howl_lstm_bwd") : HOWL_OK;
+    }
+    // the launches; with `jobs` the wide weight gradients are collected instead of launched (howl_seq_lstm_bwd runs them together
+    // with the head's), `ride` is a collected job whose blocks go into the recurrence's launch; the slab folds go to `sums`
+    void launch(hipStream_t stream, SlabSums& sums, WgradJobs* jobs, const WgradJob* ride = nullptr) const {
+        {
+        // dG_t W_hh of every step (+ the job that rides along)
+        HowlProfScope prof("lstm_bwd", stream, 2.0 * HID * G4 * (double)B * sv->t_out + (ride != nullptr ? 2.0 * (double)ride->M * ride->N * ride->K : 0.0));
+        if (!q.rows16)
+            hipLaunchKernelGGL(lstm_bwd4_kernel, dim3(q.nrec + (ride != nullptr ? wgrad_job_blocks(*ride) : 0)), dim3(B8_THREADS), 0, stream,
+                               dy, dhT, dcT, p->w_hh, lengths, (const float*)sv->gates, (const float*)sv->c, c0, sv->dgates, q.slabs_b, B,
+                               T, sv->t_out, q.nrec, ride != nullptr ? *ride : WgradJob{});
+        else
+            hipLaunchKernelGGL(lstm_bwd_kernel, dim3((B + 15) / 16), dim3(LSTM_THREADS), 0, stream, dy, dhT, dcT, (const float*)q.w_hh_b,
+                               lengths, (const float*)sv->gates, (const float*)sv->c, c0, sv->dgates, B, T, sv->t_out);
+        }
+        // dW_ih = dG^T X, dW_hh = dG^T H_prev (hseq rows t = 0..t_out-1 of each utterance), db = column sums of dG; 256 rows per K
+        // slice (up to 128 slices): the 512-row slices of the generic rule leave ~1 block per CU on these shapes.  One job for both
+        // products where the shape allows (dG -- 40 MB at 512 x 38 -- read and staged once): howl_gemm.hip.h
+        if (!wgrad_dual_gemm(sv->dgates, q.rows_g, G4, sv->hseq, q.rows_h, x, q.rows_x, M, q.rows, q.slabs_hh, g->w_hh, q.slabs_ih, g->w_ih,
+                             LSTM_WGRAD_SPLITS, &sums, jobs)) {
+            wgrad_gemm(stream, sv->dgates, q.rows_g, G4, x, q.rows_x, M, q.rows, q.slabs_ih, g->w_ih, LSTM_WGRAD_SPLITS, 256, &sums, jobs);
+            wgrad_gemm(stream, sv->dgates, q.rows_g, G4, sv->hseq, q.rows_h, HID, q.rows, q.slabs_hh, g->w_hh, LSTM_WGRAD_SPLITS, 256, &sums,
+                       jobs);
+        }
+        if (!q.rows16)   // the four-sequence recurrence left one slab of step-and-sequence sums per workgroup
+            sums.add(q.slabs_b, q.nrec, G4, g->b_ih, g->b_hh);
+        else
+            colsum(stream, sv->dgates, q.rows_g, q.rows, G4, q.slabs_b, g->b_ih, g->b_hh, 256, 64, &sums);
+    }
+};
+
+// One howl_head_bwd problem (alone, or the head half of howl_seq_lstm_bwd): the call's arguments and its plan
+struct HeadBwd {
+    const HowlHeadParams* p;
+    const HowlHeadGrads* g;
+    const HowlCtcMean* ctc_mean;
+    RowMap xm;
+    int rows, n_in, n_hid, n_out;
+    const float *x, *y1, *dy2;
+    float *dz1, *dx;
+    void* ws;
+    size_t ws_bytes;
+    HeadPlan h;
+    int plan() {      // every refusal of the call
+        HOWL_REQUIRE(ctc_mean == nullptr || (ctc_mean->nll && ctc_mean->target_lengths && ctc_mean->loss && ctc_mean->B >= 1),
+                     "howl_head_bwd: incomplete HowlCtcMean");
+        HOWL_REQUIRE(p && p->w1 && p->w2 && x && ((y1 && dy2) || (!y1 && !dy2)) && dz1 && g && g->w1 && g->b1 && g->w2 && g->b2 && ws,
+                     "howl_head_bwd: null pointer");
+        HOWL_REQUIRE(rows >= 1 && n_in >= 1 && n_hid >= 1 && n_out >= 1 && xm.inner >= 1, "howl_head_bwd: bad shape");
+        const HeadBwdOperands o{y1, dy2, dz1, dx, p->w2};
+        h = head_plan(rows, xm.inner, n_in, n_hid, n_out, 0, ws, &o);
+        HOWL_REQUIRE(h.path != HEAD_FOLD || h.seq,
+                     "howl_head_bwd: dy2 == NULL means the rows were run by howl_seq_head_ctc, which does not cover this shape");
+        return ws_bytes < h.bytes ? refuse_workspace("howl_head_bwd") : HOWL_OK;
+    }
+    // the launches; the slab folds go to `sums`, the first layer's weight gradient to `jobs` where given
+    void launch(hipStream_t stream, SlabSums& sums, WgradJobs* jobs) const {
+        const HowlCtcMean cm = ctc_mean != nullptr ? *ctc_mean : HowlCtcMean{nullptr, nullptr, 0, nullptr};
+        const int mean_block = ctc_mean != nullptr ? 1 : 0;      // the CTC loss's batch mean: one more workgroup of the thin kernels
+        if (h.path == HEAD_FOLD) {
+            if (ctc_mean != nullptr) sums.mean = SlabMean{cm.nll, cm.target_lengths, cm.B, cm.loss};     // rides in the call's fold launch
+        } else if (h.path == HEAD_ROWS) {
+            HowlProfScope prof("gemm", stream, 2.0 * (double)rows * n_in * n_hid);
+            for_n_out(n_out, [&](auto no) {
+                hipLaunchKernelGGL(head_bwd_rows_kernel<decltype(no)::value>, dim3(h.blocks + mean_block), dim3(HB_THREADS), 0, stream, y1,
+                                   dy2, rows, p->w2, p->w1, dz1, dx, h.thin_slabs, h.blocks, cm);
+            });
+        } else if (h.path == HEAD_THIN) {
+            for_n_out(n_out, [&](auto no) {
+                hipLaunchKernelGGL(head_thin_bwd_kernel<decltype(no)::value>, dim3(h.blocks + mean_block), dim3(256), 0, stream, y1, dy2,
+                                   rows, n_hid, h.rpb, p->w2, dz1, h.thin_slabs, h.blocks, cm);
+            });
+        } else {
+            if (ctc_mean != nullptr) hipLaunchKernelGGL(ctc_mean_only_kernel, dim3(1), dim3(256), 0, stream, cm);
+            gemm(stream, true, dy2, lin(n_out), 1, lin(0), p->w2, lin(n_hid), 1, rows, n_hid, n_out, 1, nullptr, 0, dz1, n_hid, 0);
+            hipLaunchKernelGGL(relu_bwd_kernel, dim3(1024), dim3(256), 0, stream, (const float*)dz1, y1, (long)rows * n_hid, dz1);
+            wgrad_gemm(stream, dy2, lin(n_out), n_out, y1, lin(n_hid), n_hid, rows, h.ws2, g->w2, 64, 512, &sums);
+            colsum(stream, dy2, lin(n_out), rows, n_out, h.scratch_b2, g->b2, nullptr, 256, 64, &sums);
+            colsum(stream, dz1, lin(n_hid), rows, n_hid, h.scratch_b1, g->b1, nullptr, 256, 64, &sums);
+        }
+        if (h.path != HEAD_GEMM) {      // the folds of a thin path's slabs
+            sums.add_strided(h.thin_slabs, h.blocks, h.slab, (long)n_out * n_hid, g->w2);
+            sums.add_strided(h.thin_slabs + (size_t)n_out * n_hid, h.blocks, h.slab, n_hid, g->b1);
+            sums.add_strided(h.thin_slabs + (size_t)(n_out + 1) * n_hid, h.blocks, h.slab, n_out, g->b2);
+        }
+        if (dx != nullptr && h.path != HEAD_FOLD && h.path != HEAD_ROWS)   // dx = dz1 W1
+            gemm(stream, true, dz1, lin(n_hid), 1, lin(0), p->w1, lin(n_in), 1, rows, n_in, n_hid, 1, nullptr, 0, dx, n_in, 0);
+        wgrad_gemm(stream, dz1, lin(n_hid), n_hid, x, xm, n_in, rows, h.first, g->w1, HEAD_W1_SPLITS, 512, &sums, jobs);
+    }
+};
 
 }  // namespace
 
 extern "C" {
 
-size_t howl_lstm_workspace_bytes(int B, int T) {
-    // packed W_hh of the 16-row recurrences (2 x 64K floats) + bias sum (512) + split-K scratch of the W_hh gradient
-    // (128 x 512 x 128) + the W_ih gradient's own scratch (128 x 512 x 96 at most) + the bias column sums' (256 x 512):
-    // three regions, so that the three final slab sums can run as one launch (the bias region holds one slab per workgroup
-    // of the four-sequence recurrence, or the 256 of the column-sum kernel)
-    const size_t bias_slabs = (size_t)(B + 3) / 4 > 256 ? (size_t)(B + 3) / 4 : 256;
-    return ((size_t)2 * 16 * 64 * 64 + G4 + (size_t)LSTM_WGRAD_SPLITS * G4 * HID + (size_t)LSTM_WGRAD_SPLITS * G4 * LSTM_MAX_IN +
-            bias_slabs * G4) * sizeof(float) + 1024;
-}
-
-// (the four-sequence recurrence multiplies x_t W_ih^T itself when M = 40: no projection launch, gx unused)
-static bool lstm_fuse_x(const HowlLstmParams* p, int B, int T, int M, int xf) {
-    return !lstm_rows16(B, T) && M == 40 && (reinterpret_cast<uintptr_t>(p->w_ih) & 15) == 0 &&
-           (size_t)B * (size_t)xf * M * sizeof(float) < ((size_t)1 << 32) && getenv("HOWL_LSTM_NO_FUSED_X") == nullptr;
-}
+size_t howl_lstm_workspace_bytes(int B, int T) { return lstm_plan(nullptr, B, T, 1, T, 0, false).bytes; }
 
 size_t howl_lstm_needs_gx(const HowlLstmParams* p, int B, int T, int M, int x_frames) {
     if (p == nullptr || p->w_ih == nullptr) return 1;
-    return lstm_fuse_x(p, B, T, M, x_frames > 0 ? x_frames : T) ? 0 : 1;
+    return lstm_plan(p, B, T, M, T, x_frames, false).fuse_x ? 0 : 1;
 }
 
 static int lstm_fwd_impl(const HowlLstmParams* p, const float* x, int B, int T, int M, const long long* lengths, const float* h0,
@@ -1350,59 +1564,42 @@ static int lstm_fwd_impl(const HowlLstmParams* p, const float* x, int B, int T, 
                                       next->layout, &ll);
         if (rc != HOWL_OK) return rc;
     }
-    HOWL_REQUIRE(B >= 1 && T >= 1 && M >= 1, "howl_lstm_fwd: bad shape");
-    HOWL_REQUIRE(sv->t_out >= 1 && sv->t_out <= T, "howl_lstm_fwd: t_out=%d outside 1..T", sv->t_out);
-    if (ws_bytes < howl_lstm_workspace_bytes(B, T)) {
-        howl_set_error("howl_lstm_fwd: workspace too small");
-        return HOWL_E_WORKSPACE;
-    }
-    float* pf = static_cast<float*>(ws);
-    float* pb = pf + 16 * 64 * 64;
-    float* bsum = pb + 16 * 64 * 64;
-    const bool rows16 = lstm_rows16(B, T);
+    const LstmPlan q = lstm_plan(p, B, T, M, sv->t_out, sv->x_frames, false, ws, next != nullptr ? &ll : nullptr);
+    HOWL_REQUIRE(q.bad[0] == 0, "howl_lstm_fwd: %s", q.bad);
+    HOWL_REQUIRE(q.fuse_x || sv->gx != nullptr, "howl_lstm_fwd: saved->gx is NULL but this shape runs the projection GEMM "
+                                                "(howl_lstm_needs_gx)");
+    if (ws_bytes < q.bytes) return refuse_workspace("howl_lstm_fwd");
     // the 16-row recurrences take packed W_hh fragments and a folded bias (one launch); the 4-row ones read the parameters
     // in place and add the bias themselves: gx = x W_ih^T (+ b_ih + b_hh)   (B*T, 512), K = M
-    if (rows16)
-        hipLaunchKernelGGL(lstm_pack_kernel, dim3(16 * 64 * 64 / 256), dim3(256), 0, stream, p->w_hh, pf, pb, p->b_ih, p->b_hh, bsum);
-    const int xf = sv->x_frames > 0 ? sv->x_frames : T;
-    HOWL_REQUIRE(xf >= T, "howl_lstm_fwd: x_frames=%d < T=%d", xf, T);
-    const bool fuse_x = lstm_fuse_x(p, B, T, M, xf);
-    HOWL_REQUIRE(fuse_x || sv->gx != nullptr, "howl_lstm_fwd: saved->gx is NULL but this shape runs the projection GEMM "
-                                              "(howl_lstm_needs_gx)");
-    if (!fuse_x)
-        gemm(stream, true, x, xf == T ? lin(M) : RowMap{T, (long)xf * M, M}, 1, lin(0), p->w_ih, lin(1), M, B * T, G4, M, 1,
-             rows16 ? bsum : nullptr, 0, sv->gx, G4, 0);
+    if (q.rows16)
+        hipLaunchKernelGGL(lstm_pack_kernel, dim3(16 * 64 * 64 / 256), dim3(256), 0, stream, p->w_hh, q.w_hh_f, q.w_hh_b, p->b_ih, p->b_hh,
+                           q.bsum);
+    if (!q.fuse_x)
+        gemm(stream, true, x, q.xf == T ? lin(M) : RowMap{T, (long)q.xf * M, M}, 1, lin(0), p->w_ih, lin(1), M, B * T, G4, M, 1, q.rows16 ? q.bsum : nullptr, 0, sv->gx, G4, 0);
     if (sv->t_out < T)   // rows of steps that never run are read (times zero) by the weight-gradient GEMM: keep them finite
         hipMemsetAsync(sv->hseq, 0, (size_t)B * (T + 1) * HID * sizeof(float), stream);
-    // h_{t-1} W_hh^T of every step (+ x_t W_ih^T where the recurrence multiplies it itself)
-    // the next batch's frontend rides in this launch when the recurrence leaves half of the device idle (HOWL_LSTM_RIDE_LOGMEL=0:
-    // as its own launch behind the recurrence, as it is whenever the four-sequence kernel with the fused projection does not run)
-    const bool ride = next != nullptr && fuse_x && (B + 3) / 4 <= howl_num_cus() / 2 && next->M <= 4 * NG_BANDED &&
-                      (getenv("HOWL_LSTM_RIDE_LOGMEL") == nullptr || getenv("HOWL_LSTM_RIDE_LOGMEL")[0] != '0');
+    // lstm_fwd4_kernel's instances: <40, true> = x_t W_ih^T inside the recurrence + the next batch's log-mel in rider blocks,
+    // <40> = the same without riders, <0> = the gates' input share from gx
+    auto fwd4 = [&](auto xm, auto ride, const float* in, const float* w_ih, int xf) {
+        constexpr int XM = decltype(xm)::value;
+        constexpr bool RIDE = decltype(ride)::value;
+        hipLaunchKernelGGL((lstm_fwd4_kernel<XM, RIDE>), dim3(q.nrec + (RIDE ? q.nb : 0)), dim3(F8_THREADS), 0, stream, in, w_ih, xf, p->w_hh,
+                           p->b_ih, p->b_hh, lengths, h0, c0, sv->gates, sv->c, sv->hseq, hT, cT, B, T, sv->t_out, q.nrec,
+                           RIDE ? ll : LogmelLaunch{}, RIDE ? q.nb : 0);
+    };
     {
-    HowlProfScope prof("lstm_fwd", stream, 2.0 * (HID + (fuse_x ? M : 0)) * G4 * (double)B * sv->t_out);
-    if (fuse_x) {
-        const int nrec = (B + 3) / 4;
-        if (ride) {
-            const int nb = std::max(1, std::min(ll.n_quads, howl_num_cus() - nrec));
-            hipLaunchKernelGGL((lstm_fwd4_kernel<40, true>), dim3(nrec + nb), dim3(F8_THREADS), 0, stream, x, p->w_ih, xf, p->w_hh, p->b_ih,
-                               p->b_hh, lengths, h0, c0, sv->gates, sv->c, sv->hseq, hT, cT, B, T, sv->t_out, nrec, ll, nb);
-        } else {
-            hipLaunchKernelGGL(lstm_fwd4_kernel<40>, dim3(nrec), dim3(F8_THREADS), 0, stream, x, p->w_ih, xf, p->w_hh, p->b_ih, p->b_hh,
-                               lengths, h0, c0, sv->gates, sv->c, sv->hseq, hT, cT, B, T, sv->t_out, nrec, LogmelLaunch{}, 0);
-        }
-    } else if (!rows16) {
-        hipLaunchKernelGGL(lstm_fwd4_kernel<0>, dim3((B + 3) / 4), dim3(F8_THREADS), 0, stream, (const float*)sv->gx,
-                           (const float*)nullptr, 0, p->w_hh, p->b_ih, p->b_hh, lengths, h0, c0, sv->gates, sv->c, sv->hseq, hT, cT, B,
-                           T, sv->t_out, (B + 3) / 4, LogmelLaunch{}, 0);
-    } else {
-        const size_t lds_fwd = (size_t)(2 * 16 * HS + 2 * 16 * 6 * HID) * sizeof(float);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fwd);
-        hipLaunchKernelGGL(lstm_fwd_kernel, dim3((B + 15) / 16), dim3(LSTM_THREADS), lds_fwd, stream, (const float*)sv->gx,
-                           (const float*)pf, lengths, h0, c0, sv->gates, sv->c, sv->hseq, hT, cT, B, T, sv->t_out);
+    // h_{t-1} W_hh^T of every step (+ x_t W_ih^T where the recurrence multiplies it itself)
+    HowlProfScope prof("lstm_fwd", stream, 2.0 * (HID + (q.fuse_x ? M : 0)) * G4 * (double)B * sv->t_out);
+    if (q.ride) fwd4(std::integral_constant<int, 40>{}, std::true_type{}, x, p->w_ih, q.xf);
+    else if (q.fuse_x) fwd4(std::integral_constant<int, 40>{}, std::false_type{}, x, p->w_ih, q.xf);
+    else if (!q.rows16) fwd4(std::integral_constant<int, 0>{}, std::false_type{}, (const float*)sv->gx, (const float*)nullptr, 0);
+    else {
+        raise_lds_limit<lstm_fwd_kernel>(LSTM_FWD16_LDS, "howl_lstm_fwd");
+        hipLaunchKernelGGL(lstm_fwd_kernel, dim3((B + 15) / 16), dim3(LSTM_THREADS), LSTM_FWD16_LDS, stream, (const float*)sv->gx,
+                           (const float*)q.w_hh_f, lengths, h0, c0, sv->gates, sv->c, sv->hseq, hT, cT, B, T, sv->t_out);
     }
     }
-    if (next != nullptr && !ride) {
+    if (next != nullptr && !q.ride) {
         const int rc = howl_logmel_fwd(next->pcm, next->B, next->L, next->ld, next->fbp, next->M, next->log_eps, next->zmuv, next->out,
                                        next->layout, stream);
         if (rc != HOWL_OK) return rc;
@@ -1424,105 +1621,36 @@ int howl_lstm_fwd_next(const HowlLstmParams* p, const float* x, int B, int T, in
     return lstm_fwd_impl(p, x, B, T, M, lengths, h0, c0, sv, hT, cT, ws, ws_bytes, next, stream);
 }
 
-// body of howl_lstm_bwd; with `jobs` the wide weight gradients are collected instead of launched (howl_seq_lstm_bwd runs them
-// together with the head's), and the slab folds go to `sums` (flushed by the caller)
-static int lstm_bwd_impl(const HowlLstmParams* p, const float* x, int B, int T, int M, const long long* lengths, const float* c0,
-                         const HowlLstmSaved* sv, const float* dy, const float* dhT, const float* dcT, const HowlLstmGrads* g,
-                         void* ws, size_t ws_bytes, hipStream_t stream, SlabSums& sums, WgradJobs* jobs,
-                         const WgradJob* ride = nullptr) {
-    HOWL_REQUIRE(p && x && sv && g && ws, "howl_lstm_bwd: null pointer");
-    HOWL_REQUIRE(dy || dhT, "howl_lstm_bwd: no incoming gradient");
-    if (ws_bytes < howl_lstm_workspace_bytes(B, T)) {
-        howl_set_error("howl_lstm_bwd: workspace too small");
-        return HOWL_E_WORKSPACE;
-    }
-    float* pf = static_cast<float*>(ws);
-    float* pb = pf + 16 * 64 * 64;
-    float* scratch = pb + 16 * 64 * 64 + G4;
-    float* scratch_ih = scratch + (size_t)LSTM_WGRAD_SPLITS * G4 * HID;
-    float* scratch_b = scratch_ih + (size_t)LSTM_WGRAD_SPLITS * G4 * LSTM_MAX_IN;
-    const int Tout = sv->t_out;
-    const bool rows16 = lstm_rows16(B, T);
-    {
-    // dG_t W_hh of every step (+ the job that rides along)
-    HowlProfScope prof("lstm_bwd", stream, 2.0 * HID * G4 * (double)B * Tout + (ride != nullptr ? 2.0 * (double)ride->M * ride->N * ride->K : 0.0));
-    if (!rows16) {
-        const int nrec = (B + 3) / 4;
-        hipLaunchKernelGGL(lstm_bwd4_kernel, dim3(nrec + (ride != nullptr ? wgrad_job_blocks(*ride) : 0)), dim3(B8_THREADS), 0, stream, dy,
-                           dhT, dcT, p->w_hh, lengths, (const float*)sv->gates, (const float*)sv->c, c0, sv->dgates, scratch_b, B, T,
-                           Tout, nrec, ride != nullptr ? *ride : WgradJob{});
-    }
-    else
-        hipLaunchKernelGGL(lstm_bwd_kernel, dim3((B + 15) / 16), dim3(LSTM_THREADS), 0, stream, dy, dhT, dcT, (const float*)pb,
-                           lengths, (const float*)sv->gates, (const float*)sv->c, c0, sv->dgates, B, T, Tout);
-    }
-    // dW_ih = dG^T X, dW_hh = dG^T H_prev (hseq rows t = 0..t_out-1 of each utterance), db = column sums of dG.  Steps
-    // t >= t_out never ran and their dG rows are never written: the reductions walk rows (b, t < t_out) only.
-    const bool full = Tout == T;
-    const RowMap rows_g = full ? lin(G4) : RowMap{Tout, (long)T * G4, G4};
-    const int xf = sv->x_frames > 0 ? sv->x_frames : T;
-    HOWL_REQUIRE(xf >= T, "howl_lstm_bwd: x_frames=%d < T=%d", xf, T);
-    const RowMap rows_x = (full && xf == T) ? lin(M) : RowMap{Tout, (long)xf * M, M};
-    const int rows = B * Tout;
-    // 256 rows per K slice (up to 128 slices): the 512-row slices of the generic rule leave ~1 block per CU on these shapes
-    HOWL_REQUIRE(M <= LSTM_MAX_IN, "howl_lstm_bwd: M=%d input features exceed the workspace layout (max %d)", M, LSTM_MAX_IN);
-    // one job for both products where the shape allows (dG -- 40 MB at 512 x 38 -- read and staged once): howl_gemm.hip.h
-    if (!wgrad_dual_gemm(sv->dgates, rows_g, G4, sv->hseq, RowMap{Tout, (long)(T + 1) * HID, HID}, x, rows_x, M, rows, scratch, g->w_hh,
-                         scratch_ih, g->w_ih, LSTM_WGRAD_SPLITS, &sums, jobs)) {
-        wgrad_gemm(stream, sv->dgates, rows_g, G4, x, rows_x, M, rows, scratch_ih, g->w_ih, LSTM_WGRAD_SPLITS, 256, &sums, jobs);
-        wgrad_gemm(stream, sv->dgates, rows_g, G4, sv->hseq, RowMap{Tout, (long)(T + 1) * HID, HID}, HID, rows, scratch, g->w_hh,
-                   LSTM_WGRAD_SPLITS, 256, &sums, jobs);
-    }
-    if (!rows16)   // the four-sequence recurrence left one slab of step-and-sequence sums per workgroup
-        sums.add(scratch_b, (B + 3) / 4, G4, g->b_ih, g->b_hh);
-    else
-        colsum(stream, sv->dgates, rows_g, rows, G4, scratch_b, g->b_ih, g->b_hh, 256, 64, &sums);
-    return HOWL_OK;
-}
-
-
 int howl_lstm_bwd(const HowlLstmParams* p, const float* x, int B, int T, int M, const long long* lengths, const float* c0,
                   const HowlLstmSaved* sv, const float* dy, const float* dhT, const float* dcT, const HowlLstmGrads* g,
                   void* ws, size_t ws_bytes, hipStream_t stream) {
-    SlabSums sums;
-    const int rc = lstm_bwd_impl(p, x, B, T, M, lengths, c0, sv, dy, dhT, dcT, g, ws, ws_bytes, stream, sums, nullptr);
+    LstmBwd lb{p, sv, g, lengths, x, c0, dy, dhT, dcT, B, T, M, ws, ws_bytes};
+    const int rc = lb.plan();
     if (rc != HOWL_OK) return rc;
+    SlabSums sums;
+    lb.launch(stream, sums, nullptr);
     if (!sums.flush(stream)) return HOWL_E_ARG;
     HOWL_CHECK_LAUNCH("howl_lstm_bwd");
     return HOWL_OK;
 }
 
-size_t howl_head_workspace_bytes(int n_in, int n_hid, int n_out) {
-    // [first layer: up to 128 split-K slabs of n_hid x n_in] [second layer, thin: HEAD_BWD_BLOCKS slabs of (n_out + 1) n_hid + n_out]
-    // (other shapes: the GEMM path's slabs of both layers)
-    const size_t first = (size_t)HEAD_W1_SPLITS * n_hid * n_in;
-    const size_t thin = (size_t)HEAD_BWD_BLOCKS * ((size_t)(n_out + 1) * n_hid + n_out);
-    const size_t general = linear_ws_floats(n_hid, n_in) + linear_ws_floats(n_out, n_hid);
-    const size_t a = first + thin + 64, b = general + 64;
-    return (a > b ? a : b) * sizeof(float);
-}
+size_t howl_head_workspace_bytes(int n_in, int n_hid, int n_out) { return head_plan(1, 1, n_in, n_hid, n_out).bytes; }
 
 int howl_head_fwd(const HowlHeadParams* p, const float* x, int rows_inner, long s_outer, long s_inner, int rows, int n_in,
                   int n_hid, int n_out, float* y1, float* y2, hipStream_t stream) {
     HOWL_REQUIRE(p && p->w1 && p->b1 && p->w2 && p->b2 && x && y1 && y2, "howl_head_fwd: null pointer");
     HOWL_REQUIRE(rows >= 1 && n_in >= 1 && n_hid >= 1 && n_out >= 1 && rows_inner >= 1, "howl_head_fwd: bad shape");
-    const bool is_thin = head_is_thin(n_hid, n_out);
+    const HeadPlan h = head_plan(rows, rows_inner, n_in, n_hid, n_out);
     const RowGemmThin second{p->w2, p->b2, y2};
     bool second_done = false;     // many rows: the second layer rides in the first layer's launch (rowgemm_kernel)
     gemm(stream, true, x, RowMap{rows_inner, s_outer, s_inner}, 1, lin(0), p->w1, lin(1), n_in, rows, n_hid, n_in, 1, p->b1, 1,
-         y1, n_hid, 0, is_thin ? &second : nullptr, n_out, &second_done);
+         y1, n_hid, 0, h.thin ? &second : nullptr, n_out, &second_done);
     if (second_done) {
-    } else if (is_thin) {
-        int blocks = (rows + 15) / 16;
-        const int cap = 4 * howl_num_cus();
-        blocks = blocks > cap ? cap : blocks;
-#define HOWL_HEAD_OUT(NO) \
-    case NO: hipLaunchKernelGGL(head_out_kernel<NO>, dim3(blocks), dim3(256), 0, stream, (const float*)y1, rows, n_hid, p->w2, p->b2, y2); break;
-        switch (n_out) {
-            HOWL_HEAD_OUT(1) HOWL_HEAD_OUT(2) HOWL_HEAD_OUT(3) HOWL_HEAD_OUT(4) HOWL_HEAD_OUT(5) HOWL_HEAD_OUT(6) HOWL_HEAD_OUT(7)
-            HOWL_HEAD_OUT(8)
-        }
-#undef HOWL_HEAD_OUT
+    } else if (h.thin) {
+        for_n_out(n_out, [&](auto no) {
+            hipLaunchKernelGGL(head_out_kernel<decltype(no)::value>, dim3(h.out_blocks), dim3(256), 0, stream, (const float*)y1, rows, n_hid, p->w2,
+                               p->b2, y2);
+        });
     } else {
         gemm(stream, true, y1, lin(n_hid), 1, lin(0), p->w2, lin(1), n_hid, rows, n_out, n_hid, 1, p->b2, 0, y2, n_out, 0);
     }
@@ -1530,103 +1658,21 @@ int howl_head_fwd(const HowlHeadParams* p, const float* x, int rows_inner, long 
     return HOWL_OK;
 }
 
-static int head_bwd_impl(const HowlHeadParams* p, const float* x, int rows_inner, long s_outer, long s_inner, int rows, int n_in,
-                         int n_hid, int n_out, const float* y1, const float* dy2, float* dz1, float* dx, const HowlHeadGrads* g,
-                         const HowlCtcMean* ctc_mean, void* ws, size_t ws_bytes, hipStream_t stream, SlabSums& sums, WgradJobs* jobs) {
-    HOWL_REQUIRE(ctc_mean == nullptr || (ctc_mean->nll && ctc_mean->target_lengths && ctc_mean->loss && ctc_mean->B >= 1),
-                 "howl_head_bwd: incomplete HowlCtcMean");
-    const HowlCtcMean cm = ctc_mean != nullptr ? *ctc_mean : HowlCtcMean{nullptr, nullptr, 0, nullptr};
-    HOWL_REQUIRE(p && p->w1 && p->w2 && x && ((y1 && dy2) || (!y1 && !dy2)) && dz1 && g && g->w1 && g->b1 && g->w2 && g->b2 && ws,
-                 "howl_head_bwd: null pointer");
-    HOWL_REQUIRE(rows >= 1 && n_in >= 1 && n_hid >= 1 && n_out >= 1 && rows_inner >= 1, "howl_head_bwd: bad shape");
-    if (ws_bytes < howl_head_workspace_bytes(n_in, n_hid, n_out)) {
-        howl_set_error("howl_head_bwd: workspace too small");
-        return HOWL_E_WORKSPACE;
-    }
-    float* first = static_cast<float*>(ws);
-    const RowMap xm{rows_inner, s_outer, s_inner};
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    bool dx_done = false;
-    if (dy2 == nullptr) {
-        // howl_seq_head_ctc ran the rows already (dz1, dx and one slab of partial sums per workgroup are in place): fold its slabs
-        SeqHeadGeom sg;
-        HOWL_REQUIRE(y1 == nullptr && rows % rows_inner == 0 && seq_head_geometry(rows / rows_inner, rows_inner, n_in, n_hid, n_out, 0, &sg),
-                     "howl_head_bwd: dy2 == NULL means the rows were run by howl_seq_head_ctc, which does not cover this shape");
-        float* thin = first + (size_t)HEAD_W1_SPLITS * n_hid * n_in;
-        if (ctc_mean != nullptr) sums.mean = SlabMean{cm.nll, cm.target_lengths, cm.B, cm.loss};     // rides in the call's fold launch
-        const long slab = (long)(n_out + 1) * n_hid + n_out;
-        sums.add_strided(thin, sg.blocks, slab, (long)n_out * n_hid, g->w2);
-        sums.add_strided(thin + (size_t)n_out * n_hid, sg.blocks, slab, n_hid, g->b1);
-        sums.add_strided(thin + (size_t)(n_out + 1) * n_hid, sg.blocks, slab, n_out, g->b2);
-        dx_done = true;
-    } else if (head_is_thin(n_hid, n_out) && dx != nullptr && n_hid == HB_HID && n_in == HB_IN && rows >= rowgemm_min_rows() &&
-        rows < (1 << 20) && al16(y1) && al16(dz1) && al16(dx) && al16(p->w2) && getenv("HOWL_GEMM_NO_ROWGEMM") == nullptr) {
-        // many rows: second layer's backward + ReLU mask + dx = dz1 W1 in one launch, one slab of partial sums per workgroup
-        float* thin = first + (size_t)HEAD_W1_SPLITS * n_hid * n_in;
-        const int ntiles = (rows + 15) / 16;
-        const int blocks = std::min(std::min(ntiles, howl_num_cus()), HEAD_BWD_BLOCKS);
-        HowlProfScope prof("gemm", stream, 2.0 * (double)rows * n_in * n_hid);
-#define HOWL_HEAD_BWD_ROWS(NO) \
-    case NO: hipLaunchKernelGGL(head_bwd_rows_kernel<NO>, dim3(blocks + (ctc_mean != nullptr ? 1 : 0)), dim3(HB_THREADS), 0, stream, y1, dy2, rows, p->w2, p->w1, dz1, dx, thin, blocks, cm); break;
-        switch (n_out) {
-            HOWL_HEAD_BWD_ROWS(1) HOWL_HEAD_BWD_ROWS(2) HOWL_HEAD_BWD_ROWS(3) HOWL_HEAD_BWD_ROWS(4) HOWL_HEAD_BWD_ROWS(5)
-            HOWL_HEAD_BWD_ROWS(6) HOWL_HEAD_BWD_ROWS(7) HOWL_HEAD_BWD_ROWS(8)
-        }
-#undef HOWL_HEAD_BWD_ROWS
-        const long slab = (long)(n_out + 1) * n_hid + n_out;
-        sums.add_strided(thin, blocks, slab, (long)n_out * n_hid, g->w2);
-        sums.add_strided(thin + (size_t)n_out * n_hid, blocks, slab, n_hid, g->b1);
-        sums.add_strided(thin + (size_t)(n_out + 1) * n_hid, blocks, slab, n_out, g->b2);
-        dx_done = true;
-    } else if (head_is_thin(n_hid, n_out)) {
-        float* thin = first + (size_t)HEAD_W1_SPLITS * n_hid * n_in;
-        int rpb = (rows + HEAD_BWD_BLOCKS - 1) / HEAD_BWD_BLOCKS;
-        rpb = (rpb + 7) / 8 * 8;
-        const int blocks = (rows + rpb - 1) / rpb;
-#define HOWL_HEAD_BWD(NO) \
-    case NO: hipLaunchKernelGGL(head_thin_bwd_kernel<NO>, dim3(blocks + (ctc_mean != nullptr ? 1 : 0)), dim3(256), 0, stream, y1, dy2, rows, n_hid, rpb, p->w2, dz1, thin, blocks, cm); break;
-        switch (n_out) {
-            HOWL_HEAD_BWD(1) HOWL_HEAD_BWD(2) HOWL_HEAD_BWD(3) HOWL_HEAD_BWD(4) HOWL_HEAD_BWD(5) HOWL_HEAD_BWD(6) HOWL_HEAD_BWD(7)
-            HOWL_HEAD_BWD(8)
-        }
-#undef HOWL_HEAD_BWD
-        const long slab = (long)(n_out + 1) * n_hid + n_out;
-        sums.add_strided(thin, blocks, slab, (long)n_out * n_hid, g->w2);
-        sums.add_strided(thin + (size_t)n_out * n_hid, blocks, slab, n_hid, g->b1);
-        sums.add_strided(thin + (size_t)(n_out + 1) * n_hid, blocks, slab, n_out, g->b2);
-    } else {
-        // general shapes: second layer by the GEMM path (its own folds), ReLU mask, then the first layer below
-        if (ctc_mean != nullptr) hipLaunchKernelGGL(ctc_mean_only_kernel, dim3(1), dim3(256), 0, stream, cm);
-        float* ws2 = first + linear_ws_floats(n_hid, n_in);
-        float* scratch_b2 = ws2 + (size_t)HEAD_W1_SPLITS * n_out * n_hid;
-        gemm(stream, true, dy2, lin(n_out), 1, lin(0), p->w2, lin(n_hid), 1, rows, n_hid, n_out, 1, nullptr, 0, dz1, n_hid, 0);
-        hipLaunchKernelGGL(relu_bwd_kernel, dim3(1024), dim3(256), 0, stream, (const float*)dz1, y1, (long)rows * n_hid, dz1);
-        wgrad_gemm(stream, dy2, lin(n_out), n_out, y1, lin(n_hid), n_hid, rows, ws2, g->w2, 64, 512, &sums);
-        colsum(stream, dy2, lin(n_out), rows, n_out, scratch_b2, g->b2, nullptr, 256, 64, &sums);
-        float* scratch_b1 = first + (size_t)HEAD_W1_SPLITS * n_hid * n_in;
-        colsum(stream, dz1, lin(n_hid), rows, n_hid, scratch_b1, g->b1, nullptr, 256, 64, &sums);
-    }
-    if (dx != nullptr && !dx_done)   // dx = dz1 W1
-        gemm(stream, true, dz1, lin(n_hid), 1, lin(0), p->w1, lin(n_in), 1, rows, n_in, n_hid, 1, nullptr, 0, dx, n_in, 0);
-    wgrad_gemm(stream, dz1, lin(n_hid), n_hid, x, xm, n_in, rows, first, g->w1, HEAD_W1_SPLITS, 512, &sums, jobs);
-    return HOWL_OK;
-}
-
 int howl_head_bwd(const HowlHeadParams* p, const float* x, int rows_inner, long s_outer, long s_inner, int rows, int n_in,
                   int n_hid, int n_out, const float* y1, const float* dy2, float* dz1, float* dx, const HowlHeadGrads* g,
                   const HowlCtcMean* ctc_mean, void* ws, size_t ws_bytes, hipStream_t stream) {
-    SlabSums sums;
-    const int rc = head_bwd_impl(p, x, rows_inner, s_outer, s_inner, rows, n_in, n_hid, n_out, y1, dy2, dz1, dx, g, ctc_mean, ws,
-                                 ws_bytes, stream, sums, nullptr);
+    HeadBwd hb{p, g, ctc_mean, RowMap{rows_inner, s_outer, s_inner}, rows, n_in, n_hid, n_out, x, y1, dy2, dz1, dx, ws, ws_bytes};
+    const int rc = hb.plan();
     if (rc != HOWL_OK) return rc;
+    SlabSums sums;
+    hb.launch(stream, sums, nullptr);
     if (!sums.flush(stream)) return HOWL_E_ARG;
     HOWL_CHECK_LAUNCH("howl_head_bwd");
     return HOWL_OK;
 }
 
 int howl_seq_head_ctc_supported(int B, int T, int n_in, int n_hid, int n_out, int max_target_length) {
-    SeqHeadGeom g;
-    return seq_head_geometry(B, T, n_in, n_hid, n_out, max_target_length, &g) ? 1 : 0;
+    return B >= 1 && T >= 1 && head_plan((long)B * T, T, n_in, n_hid, n_out, max_target_length).seq ? 1 : 0;
 }
 
 int howl_seq_head_ctc(const HowlHeadParams* p, const float* x, long s_outer, long s_inner, int B, int T, int n_in, int n_hid, int n_out,
@@ -1638,33 +1684,21 @@ int howl_seq_head_ctc(const HowlHeadParams* p, const float* x, long s_outer, lon
     HOWL_REQUIRE(blank >= 0 && blank < n_out && max_target_length >= 0, "howl_seq_head_ctc: bad blank / target length");
     HOWL_REQUIRE(B == 1 || tgt_stride >= max_target_length,
                  "howl_seq_head_ctc: target rows of stride %ld overlap (max_target_length %d)", tgt_stride, max_target_length);
-    SeqHeadGeom g;
-    HOWL_REQUIRE(seq_head_geometry(B, T, n_in, n_hid, n_out, max_target_length, &g),
+    const HeadPlan h = B >= 1 && T >= 1 ? head_plan((long)B * T, T, n_in, n_hid, n_out, max_target_length, head_ws) : HeadPlan{};
+    HOWL_REQUIRE(h.seq,
                  "howl_seq_head_ctc: B=%d T=%d (%d -> %d -> %d, targets <= %d) is outside the fused launch's range "
                  "(howl_seq_head_ctc_supported; use howl_head_fwd + howl_ctc_loss + howl_seq_lstm_bwd)", B, T, n_in, n_hid, n_out,
                  max_target_length);
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     HOWL_REQUIRE(al16(x) && al16(p->w1) && al16(p->b1) && al16(p->w2) && al16(dz1) && al16(dhs) && (s_outer & 3) == 0 && (s_inner & 3) == 0,
                  "howl_seq_head_ctc: 16-byte aligned operands");
-    if (head_ws_bytes < howl_head_workspace_bytes(n_in, n_hid, n_out)) {
-        howl_set_error("howl_seq_head_ctc: workspace too small");
-        return HOWL_E_WORKSPACE;
-    }
-    float* thin = static_cast<float*>(head_ws) + (size_t)HEAD_W1_SPLITS * n_hid * n_in;
+    if (head_ws_bytes < h.bytes) return refuse_workspace("howl_seq_head_ctc");
     const SeqHeadArgs a{x, s_outer, s_inner, p->w1, p->b1, p->w2, p->b2, y2, targets, tgt_stride, max_target_length, input_lengths, target_lengths, blank,
-                        nll, dz1, dhs, thin, B, T, g.U, g.ngroups};
+                        nll, dz1, dhs, h.thin_slabs, B, T, h.U, h.ngroups};
     HowlProfScope prof("gemm", stream, 4.0 * (double)B * T * n_in * n_hid);
-#define HOWL_SEQ_HEAD(NO)                                                                                                        \
-    case NO: {                                                                                                                   \
-        static thread_local size_t granted[16] = {};                                                                             \
-        howl_raise_lds(reinterpret_cast<const void*>(seq_head_ctc_kernel<NO>), g.lds_bytes, granted, "howl_seq_head_ctc");        \
-        hipLaunchKernelGGL(seq_head_ctc_kernel<NO>, dim3(g.blocks), dim3(SH_THREADS), g.lds_bytes, stream, a);                   \
-    } break;
-    switch (n_out) {
-        HOWL_SEQ_HEAD(1) HOWL_SEQ_HEAD(2) HOWL_SEQ_HEAD(3) HOWL_SEQ_HEAD(4) HOWL_SEQ_HEAD(5) HOWL_SEQ_HEAD(6) HOWL_SEQ_HEAD(7)
-        HOWL_SEQ_HEAD(8)
-    }
-#undef HOWL_SEQ_HEAD
+    for_n_out(n_out, [&](auto no) {
+        raise_lds_limit<seq_head_ctc_kernel<decltype(no)::value>>(h.lds_bytes, "howl_seq_head_ctc");
+        hipLaunchKernelGGL(seq_head_ctc_kernel<decltype(no)::value>, dim3(h.seq_blocks), dim3(SH_THREADS), h.lds_bytes, stream, a);
+    });
     HOWL_CHECK_LAUNCH("howl_seq_head_ctc");
     return HOWL_OK;
 }
@@ -1678,21 +1712,19 @@ int howl_seq_lstm_bwd(const HowlHeadParams* hp, int n_hid, int n_out, const floa
     HOWL_REQUIRE(adamw == nullptr || (adamw->p && adamw->g && adamw->m && adamw->v && adamw->n >= 1 && adamw->step >= 1),
                  "howl_seq_lstm_bwd: incomplete HowlAdamW");
     HOWL_REQUIRE(sv->t_out == T, "howl_seq_lstm_bwd: t_out=%d != T=%d (use howl_head_bwd + howl_lstm_bwd)", sv->t_out, T);
+    // the head reads the hidden states h_1 .. h_T in place: row (b, t) of hseq (B, T + 1, 128) at offset 128
+    HeadBwd hb{hp, hg, ctc_mean, RowMap{T, (long)(T + 1) * HID, HID}, B * T, HID, n_hid, n_out, sv->hseq + HID, y1, dy2, dz1, dhs, head_ws,
+               head_ws_bytes};
+    LstmBwd lb{p, sv, g, lengths, x, c0, dhs, nullptr, nullptr, B, T, M, ws, ws_bytes};
+    int rc = hb.plan();
+    if (rc == HOWL_OK) rc = lb.plan();
+    if (rc != HOWL_OK) return rc;
     SlabSums sums;
     WgradJobs jobs;
-    // the head reads the hidden states h_1 .. h_T in place: row (b, t) of hseq (B, T + 1, 128) at offset 128
-    int rc = head_bwd_impl(hp, sv->hseq + HID, T, (long)(T + 1) * HID, HID, B * T, HID, n_hid, n_out, y1, dy2, dz1, dhs, hg, ctc_mean,
-                           head_ws, head_ws_bytes, stream, sums, &jobs);
-    if (rc != HOWL_OK) return rc;
-    // The head's first-layer weight gradient (dz1^T H) depends on nothing the LSTM's backward produces, and the four-sequence
-    // recurrence occupies (B + 3) / 4 CUs for its 38-81 dependent steps: while that leaves at least half of the device idle the
-    // job's blocks ride in the recurrence's launch (lstm_bwd4_kernel: 18 us of the 65-us job launch at 512 x 38).  HOWL_LSTM_RIDE:
-    // "lane" = the same job on the library's side lane instead (two cross-queue waits on the critical path: measured 9 us worse),
-    // "0" = behind the recurrence with the other weight gradients (round 4).
-    const char* ride_env = getenv("HOWL_LSTM_RIDE");
-    const bool idle_half = jobs.count == 1 && !lstm_rows16(B, T) && (B + 3) / 4 <= howl_num_cus() / 2;
-    const bool as_ride = idle_half && jobs.j[0].tn == 128 && (ride_env == nullptr || ride_env[0] == '1');
-    HowlSideLane* lane = idle_half && ride_env != nullptr && ride_env[0] == 'l' ? howl_side_lane() : nullptr;
+    hb.launch(stream, sums, &jobs);
+    // where the head's first-layer weight gradient runs (LstmPlan::head_ride), if it was collected as the one 128-column job
+    const bool as_ride = jobs.count == 1 && lb.q.head_ride == RIDE_LAUNCH && jobs.j[0].tn == 128;
+    HowlSideLane* lane = jobs.count == 1 && lb.q.head_ride == RIDE_LANE ? howl_side_lane() : nullptr;
     WgradJob ride{};
     if (as_ride) {
         ride = jobs.j[0];
@@ -1702,14 +1734,10 @@ int howl_seq_lstm_bwd(const HowlHeadParams* hp, int n_hid, int n_out, const floa
         howl_lane_fork(lane, stream);
         wgrad_jobs_flush(lane->stream, jobs);
     }
-    rc = lstm_bwd_impl(p, x, B, T, M, lengths, c0, sv, dhs, nullptr, nullptr, g, ws, ws_bytes, stream, sums, &jobs, as_ride ? &ride : nullptr);
-    if (rc != HOWL_OK) {
-        if (lane != nullptr) howl_lane_join(lane, stream);
-        return rc;
-    }
+    lb.launch(stream, sums, &jobs, as_ride ? &ride : nullptr);
     wgrad_jobs_flush(stream, jobs);
     if (lane != nullptr) howl_lane_join(lane, stream);
-    if (adamw != nullptr && sums.covers(adamw->g, adamw->n) && getenv("HOWL_NO_FOLD_ADAMW") == nullptr) {
+    if (adamw != nullptr && lb.q.fold_adamw && sums.covers(adamw->g, adamw->n)) {
         // every gradient of the model leaves this call through the fold: the optimiser step rides in it
         const SlabAdamW opt{adamw->p, adamw->g, adamw->m, adamw->v,
                             howl_adamw_coef(adamw->lr, adamw->beta1, adamw->beta2, adamw->eps, adamw->weight_decay, adamw->step,
@@ -1726,6 +1754,5 @@ int howl_seq_lstm_bwd(const HowlHeadParams* hp, int n_hid, int n_out, const floa
     HOWL_CHECK_LAUNCH("howl_seq_lstm_bwd");
     return HOWL_OK;
 }
-
 
 }  // extern "C"

@@ -504,3 +504,60 @@ def test_head_ctc_and_head_backward_rows_in_one_launch(monkeypatch, B, T, odd):
     for n, ga in zip(names, a[2]):
         r = sd[n].grad
         assert (ga - r).abs().max().item() < 1e-4 * max(1.0, r.abs().max().item()), n
+
+
+# ---- refused calls launch nothing (bodies in tests/lstm_refusal_util.py, shared with tests/test_gpu_lstm.py)
+@pytest.fixture
+def arena():
+    from guard_mem import Arena
+    return Arena()
+
+
+def test_refused_lstm_fwd_short_feature_rows(lib, arena):
+    import lstm_refusal_util as u
+    u.check_fwd_x_frames(arena, lib)
+
+
+def test_refused_lstm_fwd_without_projection_buffer(lib, arena, monkeypatch):
+    import lstm_refusal_util as u
+    u.check_fwd_gx_null(arena, lib, monkeypatch)
+
+
+def test_refused_lstm_bwd_too_many_features(lib, arena):
+    import lstm_refusal_util as u
+    u.check_bwd_too_many_features(arena, lib)
+
+
+def test_refused_lstm_bwd_short_feature_rows(lib, arena):
+    import lstm_refusal_util as u
+    u.check_bwd_x_frames(arena, lib)
+
+
+def test_refused_lstm_bwd_t_out_beyond_T(lib, arena):
+    import lstm_refusal_util as u
+    u.check_bwd_t_out(arena, lib)
+
+
+def test_refused_lstm_bwd_short_workspace(lib, arena):
+    import lstm_refusal_util as u
+    u.check_bwd_workspace(arena, lib)
+
+
+def test_refused_seq_lstm_bwd_short_lstm_workspace_with_dy2(lib, arena):
+    import lstm_refusal_util as u
+    u.check_seq_bwd_workspace_with_dy2(arena, lib)
+
+
+def test_refused_seq_lstm_bwd_short_lstm_workspace_after_seq_head_ctc(lib, arena, monkeypatch):
+    import lstm_refusal_util as u
+    u.check_seq_bwd_workspace_after_seq_head_ctc(arena, lib, monkeypatch)
+
+
+def test_refused_lstm_fwd_next_with_a_refused_frontend(lib, arena):
+    import lstm_refusal_util as u
+    u.check_fwd_next_refused_frontend(arena, lib)
+
+
+def test_workspace_size_queries_are_the_recorded_ones(lib):
+    import lstm_refusal_util as u
+    u.check_size_queries(lib)

@@ -493,3 +493,68 @@ def test_head_ctc_and_head_backward_rows_in_one_launch(B, T, monkeypatch):
         else:
             assert torch.equal(ga, gb), n
     assert maxerr(a[3], b[3]) < 2e-5          # three AdamW steps (sign-like first steps amplify the regrouped sums' last bits)
+
+
+# ---- refused calls launch nothing (bodies in tests/lstm_refusal_util.py, the emulator twins are in tests/test_emu_lstm.py)
+@pytest.fixture
+def lib():
+    from howl_amd import lib as hl
+    return hl.get()
+
+
+@pytest.fixture
+def arena():
+    from guard_mem import Banded
+    al = Banded("cuda")
+    yield al
+    al.check()      # no sentinel band around any buffer changed
+
+
+def test_refused_lstm_fwd_short_feature_rows(lib, arena):
+    import lstm_refusal_util as u
+    u.check_fwd_x_frames(arena, lib)
+
+
+def test_refused_lstm_fwd_without_projection_buffer(lib, arena, monkeypatch):
+    import lstm_refusal_util as u
+    u.check_fwd_gx_null(arena, lib, monkeypatch)
+
+
+def test_refused_lstm_bwd_too_many_features(lib, arena):
+    import lstm_refusal_util as u
+    u.check_bwd_too_many_features(arena, lib)
+
+
+def test_refused_lstm_bwd_short_feature_rows(lib, arena):
+    import lstm_refusal_util as u
+    u.check_bwd_x_frames(arena, lib)
+
+
+def test_refused_lstm_bwd_t_out_beyond_T(lib, arena):
+    import lstm_refusal_util as u
+    u.check_bwd_t_out(arena, lib)
+
+
+def test_refused_lstm_bwd_short_workspace(lib, arena):
+    import lstm_refusal_util as u
+    u.check_bwd_workspace(arena, lib)
+
+
+def test_refused_seq_lstm_bwd_short_lstm_workspace_with_dy2(lib, arena):
+    import lstm_refusal_util as u
+    u.check_seq_bwd_workspace_with_dy2(arena, lib)
+
+
+def test_refused_seq_lstm_bwd_short_lstm_workspace_after_seq_head_ctc(lib, arena, monkeypatch):
+    import lstm_refusal_util as u
+    u.check_seq_bwd_workspace_after_seq_head_ctc(arena, lib, monkeypatch)
+
+
+def test_refused_lstm_fwd_next_with_a_refused_frontend(lib, arena):
+    import lstm_refusal_util as u
+    u.check_fwd_next_refused_frontend(arena, lib)
+
+
+def test_workspace_size_queries_are_the_recorded_ones(lib):
+    import lstm_refusal_util as u
+    u.check_size_queries(lib)
