@@ -89,6 +89,13 @@ class HowlMbWsLayer(ctypes.Structure):
                                      "nslab", "group_rows")]
 
 
+class HowlDecideConfig(ctypes.Structure):
+    """``HowlDecideConfig`` of ``include/howl_hip_decide.h``: a host struct; ``weights`` / ``color`` are device pointers."""
+    _fields_ = [("mode", c_int), ("C", c_int), ("blank", c_int), ("negative", c_int), ("threshold", c_double), ("smoothing_ms", c_double),
+                ("window_ms", c_double), ("tolerance_ms", c_double), ("seq_len", c_int), ("sequence", c_int * 16), ("weights", P),
+                ("color", P)]
+
+
 SIGNATURES = {
     "howl_version": [POINTER(c_int), POINTER(c_int)],
     "howl_profile_enable": [c_int],
@@ -174,6 +181,13 @@ LSTM_STREAM_SIGNATURES = {
 }
 LSTM_STREAM_SIZE_FUNCS = {"howl_lstm_stream_supported": [c_int, c_int, c_int]}
 
+# The decision-logic entry points of ``include/howl_hip_decide.h`` (their own tables again: ``tests/test_emu_decide.py`` checks
+# them against that header)
+DECIDE_SIGNATURES = {
+    "howl_decide_clips": [POINTER(HowlDecideConfig), P, c_long, c_long, c_int, c_int, P, P, P, P, P, P, P, P, P, c_long, P, STREAM],
+}
+DECIDE_SIZE_FUNCS = {"howl_decide_supported": [POINTER(HowlDecideConfig), c_int]}
+
 
 class HowlHipError(RuntimeError):
     pass
@@ -190,11 +204,11 @@ class Library:
         self.cdll = ctypes.CDLL(str(path))
         self.cdll.howl_last_error.restype = c_char_p
         self.cdll.howl_last_error.argtypes = []
-        for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES, **LSTM_STREAM_SIGNATURES}.items():
+        for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES, **LSTM_STREAM_SIGNATURES, **DECIDE_SIGNATURES}.items():
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = c_int
             fn.argtypes = argtypes
-        for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS, **LSTM_STREAM_SIZE_FUNCS}.items():
+        for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS, **LSTM_STREAM_SIZE_FUNCS, **DECIDE_SIZE_FUNCS}.items():
             fn = getattr(self.cdll, name)
             fn.restype = c_size_t
             fn.argtypes = argtypes

@@ -322,3 +322,33 @@ def lstm_stream_chunks(lstm_prm, head_prm, pcm, fbp, n_mels, zmuv_pair, n_labels
                     _p(fbp), int(n_mels), log_eps, _p(zmuv_pair, allow_none=True), _p(h, allow_none=True), _p(c, allow_none=True),
                     int(n_labels), 1 if last_only else 0, _p(probs), _p(logits, allow_none=True), probs.stride(0), _stream())
     return probs
+
+
+def decide_supported(cfg, t_max: int) -> bool:
+    return bool(_lib.get().cdll.howl_decide_supported(ctypes.byref(cfg), int(t_max)))
+
+
+def decide_clips(cfg, probs, n_frames, delta_ms, t_max: int, weighted=None):
+    """``howl_decide_clips`` on (N, >= t_max, C) probabilities (unit class stride, any clip / frame stride): ONE launch of the
+    engines' decision logic.  ``cfg``: a ``HowlDecideConfig`` record; ``n_frames`` (N) int32 and ``delta_ms`` (N) float64 on the
+    device.  -> (ints (4, N) int32: present, status, n_labels, first_kept; end_time (N) float64; hist_time (N, t_max) float64;
+    hist_label (N, t_max) int32), all on the device; only the first n_labels entries of a history row are written.  The two history
+    tensors are allocated in full for every call: 12 bytes x N x t_max (1 MB for 64 clips of 1300 frames; 805 MB at the range's corner of
+    8192 x 8192, where a caller passes the clips in groups)."""
+    if probs.dim() != 3 or probs.size(2) != cfg.C or probs.size(1) < t_max:
+        raise ValueError(f"probs must be (N, >= {t_max}, {cfg.C}), got {tuple(probs.shape)}")
+    if probs.stride(2) != 1:
+        probs = probs.contiguous()
+    if not on_device(probs) or probs.dtype != torch.float32:
+        _p(probs)
+    N, dev = probs.size(0), probs.device
+    ints = torch.empty((4, N), dtype=torch.int32, device=dev)
+    end_time = torch.empty(N, dtype=torch.float64, device=dev)
+    ld = max(int(t_max), 1)
+    hist_time = torch.empty((N, ld), dtype=torch.float64, device=dev)
+    hist_label = torch.empty((N, ld), dtype=torch.int32, device=dev)
+    _lib.get().call("howl_decide_clips", ctypes.byref(cfg), ctypes.c_void_p(probs.data_ptr()), probs.stride(0), probs.stride(1), N, int(t_max),
+                    _p(n_frames, torch.int32), _p(delta_ms, torch.float64), _p(ints[0], torch.int32), _p(ints[1], torch.int32),
+                    _p(ints[2], torch.int32), _p(ints[3], torch.int32), _p(end_time, torch.float64), _p(hist_time, torch.float64),
+                    _p(hist_label, torch.int32), ld, _p(weighted, allow_none=True), _stream())
+    return ints, end_time, hist_time, hist_label

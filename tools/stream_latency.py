@@ -10,7 +10,13 @@ is).  Prints one JSON line.  ``--windows`` / ``--repeats`` shorten a run (a prof
 ``--model seq-lstm``: the same protocol for ``InferenceEngine.infer`` (LstmStreamSession): (a) 8000-sample chunks (what the live
 client feeds), (b) 16000-sample chunks, both with the state carried from call to call; (c) ``infer_many`` on 64 clips of 1 - 3 s
 against the clip-by-clip ``[reset(); infer(clip)]`` loop (per CALL of 64 clips; ``--windows`` / 20 calls per repeat); and the
-kernel alone between two HIP events for each of the three shapes."""
+kernel alone between two HIP events for each of the three shapes.
+
+``--model decide``: case (c)'s 64 clips through ``infer_many`` with the decision logic on the host and on the device
+(``device_decisions`` off / on, DeviceDecider), alternating repeat by repeat, in one process: (d) ``InferenceEngine`` (seq-lstm,
+``HOWL_STREAM_FUSED=1``) with the settings of (c), (e) the same with the blank weighted down so that most frames reach the smoother
+and the matcher, (f) ``FrameInferenceEngine`` (res8) on the same clips; and ``howl_decide_clips`` alone between two HIP events on
+the probabilities of each.  Each pair is checked for equal results first."""
 import argparse
 import json
 import os
@@ -32,10 +38,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--fused-only", action="store_true", help="skip the eager path (a kernel-trace pass over the one launch)")
     ap.add_argument("--eager-only", action="store_true", help="seq-lstm: skip the fused path (a kernel-trace pass over the launch chain)")
-    ap.add_argument("--model", choices=["res8", "seq-lstm"], default="res8")
+    ap.add_argument("--model", choices=["res8", "seq-lstm", "decide"], default="res8")
     args = ap.parse_args()
     if args.model == "seq-lstm":
         return main_seq_lstm(args)
+    if args.model == "decide":
+        return main_decide(args)
     import torch
     from howl_amd.context import InferenceContext
     from howl_amd.data.transform.operator import ZmuvTransform
@@ -213,6 +221,104 @@ def main_seq_lstm(args):
             us.append(e0.elapsed_time(e1) * 1e3)
         kernel[name] = round(statistics.median(us[10:]), 2)
     out["launch_us_median_between_hip_events"] = kernel
+    torch.cuda.synchronize()
+    print(json.dumps(out), flush=True)
+
+
+def main_decide(args):
+    import numpy as np
+    import torch
+    from howl_amd.context import InferenceContext
+    from howl_amd.data.transform.operator import ZmuvTransform
+    from howl_amd.data.transform.transform import StandardAudioTransform
+    from howl_amd.model import RegisteredModel
+    from howl_amd.model.decision import DeviceDecider
+    from howl_amd.model.inference import FrameInferenceEngine, InferenceEngine
+    from howl_amd.utils.synth import res8_closed_form_state, synthetic_pcm
+    dev = torch.device("cuda:0")
+    std = StandardAudioTransform().to(dev).eval()
+    zmuv = ZmuvTransform().to(dev)
+    clips = synthetic_pcm(8, 160000, seed=77).to(dev)
+    zmuv.update(std(clips[:1, :16000]))
+    rng = np.random.default_rng(7)
+    sizes = [int(v) for v in rng.integers(16000, 48001, 64)]           # case (c)'s clips
+    many = [clips[i % 8, :n].contiguous() for i, n in enumerate(sizes)]
+
+    ctx = InferenceContext(["hey", "fire", "fox"], token_type="word", use_blank=True)
+    torch.manual_seed(2024)
+    lstm = RegisteredModel.find_registered_class("seq-lstm")(ctx.num_labels).to(dev).eval().streaming()
+    seq = InferenceEngine(lstm, zmuv, ctx)
+    seq.fused_chunks = True
+    seq.sequence = [0, 1, 2, 0, 1, 2, 0, 1, 2]                         # never present: every call walks all of its frames
+    fctx = InferenceContext(["hey", "fire", "fox"], token_type="word", use_blank=False)
+    res8 = RegisteredModel.find_registered_class("res8")(fctx.num_labels).to(dev)
+    res8.load_state_dict(res8_closed_form_state(fctx.num_labels), strict=False)
+    res8.eval()
+    frame = FrameInferenceEngine(500, 63, res8, zmuv, fctx)
+    frame.sequence = [0, 1, 2, 0, 1, 2, 0, 1, 2]
+
+    def run(engine, on, n):
+        engine.device_decisions = on
+        times = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            engine.infer_many(many)
+            times.append(time.perf_counter() - t0)
+        return times
+
+    def both(engine, calls, warm):
+        engine.device_decisions = False
+        want = (engine.infer_many(many), [list(h) for h in engine.clip_histories])
+        engine.device_decisions = True
+        assert (engine.infer_many(many), engine.clip_histories) == want, "the device decisions differ from the host replay"
+        for on in (False, True):
+            run(engine, on, warm)
+        med = {True: [], False: []}
+        for _ in range(args.repeats):
+            for on in (False, True):
+                med[on].append(statistics.median(run(engine, on, calls)) * 1e6)
+        return {"calls_per_repeat": calls, "history_entries_per_call": sum(len(h) for h in want[1]),
+                "host_decisions_us_medians": [round(v, 2) for v in med[False]], "device_decisions_us_medians": [round(v, 2) for v in med[True]]}
+
+    calls, warm = max(2, args.windows // 20), max(1, args.warmup // 20)
+    out = {"metric": "infer_many wall time per call of 64 clips of 1 - 3 s, us (host copy included; median of each repeat), decision logic "
+                     "on the host against DeviceDecider", "frames_per_call_sequence_engine": sum(1 + n // 200 for n in sizes)}
+    out["d_sequence_engine_as_case_c"] = both(seq, calls, warm)
+    seq.inference_weights = np.array([1.0, 1.0, 1.0, 1.0, 0.01])
+    out["e_sequence_engine_blank_weighted_down"] = both(seq, calls, warm)
+    out["f_frame_engine_res8"] = both(frame, calls, warm)
+    out["f_frame_engine_res8"]["windows_per_call"] = sum(len(p) for p in frame.window_probabilities_many(many))
+
+    # the decision launch alone, between two HIP events, on the probabilities of each case
+    def launch_alone(decider, probs, n_frames, deltas):
+        from howl_amd import ops
+        cfg, keep = decider._config(dev)
+        nf = torch.tensor(n_frames, dtype=torch.int32, device=dev)
+        dl = torch.tensor(deltas, dtype=torch.float64, device=dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        us = []
+        for _ in range(60):
+            e0.record()
+            ops.decide_clips(cfg, probs, nf, dl, max(n_frames))
+            e1.record()
+            e1.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        return round(statistics.median(us[10:]), 2)
+
+    session = lstm.stream_session(std, zmuv)
+    pad = torch.nn.utils.rnn.pad_sequence(many, batch_first=True)
+    probs, _ = session.probabilities(pad, n_samples=torch.tensor(sizes, dtype=torch.int64, device=dev), return_state=False)
+    frames = [1 + n // 200 for n in sizes]
+    deltas = [int(n / 16000 * 1000) / f for n, f in zip(sizes, frames)]
+    alone = {"e_N64_sequence_mode_blank_weighted_down": launch_alone(DeviceDecider.from_engine(seq, 0), probs, frames, deltas)}
+    seq.inference_weights = 1
+    alone["d_N64_sequence_mode"] = launch_alone(DeviceDecider.from_engine(seq, 0), probs, frames, deltas)
+    (members, wprobs), = frame._window_probabilities_device(many)
+    counts = [n for _, n, _ in members]
+    padded = torch.nn.utils.rnn.pad_sequence(list(wprobs.split(counts)), batch_first=True)
+    alone["f_N64_frame_mode"] = launch_alone(DeviceDecider.from_engine(frame, 1), padded, counts, [63.0] * len(counts))
+    out["decide_launch_us_median_between_hip_events"] = alone
     torch.cuda.synchronize()
     print(json.dumps(out), flush=True)
 
