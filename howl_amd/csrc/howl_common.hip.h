@@ -24,6 +24,14 @@ typedef __attribute__((address_space(3))) float lds_f32;
 // part) and re-adds the constant in front of each ds_read when it exceeds the 16-bit offset field (the 3x3 forward K loop
 // carried 43 v_add_u32 per 45 MFMAs, and vector instructions do not overlap the matrix pipe on this part).
 #define HOWL_OPAQUE_LDS(p) HOWL_OPAQUE_V(p)
+// Pins the instruction order at this point: the compiler's scheduler moves nothing across it (no code is emitted).  In a K loop
+// written "operands of step s+1, then the MFMAs of step s" it keeps the reads in front of those MFMAs -- left alone the
+// scheduler sinks them to their first use, and every wait in front of an MFMA then covers a whole LDS round trip.
+#if defined(HIPEMU)
+#define HOWL_SCHED_PIN() ((void)0)
+#else
+#define HOWL_SCHED_PIN() __builtin_amdgcn_sched_barrier(0)
+#endif
 
 #define HOWL_OK 0
 #define HOWL_E_ARG (-1)       // bad argument (shape / null pointer / unsupported size)

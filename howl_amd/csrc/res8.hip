@@ -221,6 +221,7 @@ __device__ __forceinline__ void k_run(KCursor<NTW>& k, f32x4 (&acc)[NTW], int CS
                 for (int i = 0; i < NTW; ++i) na[i] = k.ap[i][0];
                 nb = k.bp[0];
             }
+            HOWL_SCHED_PIN();      // the reads above stay above: one k-step (NTW MFMAs) between a request and its first use
 #pragma unroll
             for (int i = 0; i < NTW; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(k.a[i], k.b, acc[i], 0, 0, 0);
 #pragma unroll
@@ -358,35 +359,75 @@ __device__ __forceinline__ void bn_relu_bwd_pair(const SlotVal& v, const float* 
     dz.y = t1 > 0.0f ? ds.y : 0.0f;
 }
 
-template <int MODE>
-__device__ __forceinline__ void slot_write(const SlotVal& v, const StageCfg& cfg, size_t base, int i2, int pkj, float* tile,
-                                           const float* lm, bool zero = false /* a row beyond the strip's valid ones: see StripGeom */) {
-    HOWL_OPAQUE_V(pkj);
-    if (pkj < 0) return;
-    const int c = pkj >> 20;
-    float v0 = v.a.x, v1 = v.a.y;
+// The LDS writes (and ds_i stores) of one staging burst: slots J0 .. J0 + N - 1 of a region, slot J0 + j from v[j].
+//   1. every loaded value is taken at the top, under no branch: the one wait for the burst's loads stands here, on every path (a
+//      value first used under a lane predicate or a run-time mode leaves its load "pending" on the other path, and the compiler
+//      then drains the memory counter -- stores included -- at every join behind it);
+//   2. what goes into the tile (and into ds_i) is straight-line arithmetic, one mode branch per burst; slots without an element
+//      compute on the region's first element and write nothing;
+//   3. all tile writes, then the ds_i stores behind them, fire-and-forget: this ISA counts stores and loads in one counter, and the
+//      next wait on it is the one for the next slots' loads, two K groups later.  The store's address is slot_load's: uniform base
+//      + a 32-bit lane offset made where it is used (hoisted out of the utterance loop it was nine 64-bit per-lane addresses,
+//      four of them spilled).
+// `zmask` bit J0 + j: the slot lies in a row beyond the strip's valid ones (StripGeom) and is written as zero.
+template <int MODE, int N, int J0, int NSL>
+__device__ __forceinline__ void burst_write(const SlotVal* v, const StageCfg& cfg, size_t base, int tid, const int (&pk)[NSL],
+                                            float* tile, const float* lm, unsigned zmask = 0u) {
+    static_assert(J0 + N <= NSL, "slots");
+    int pkj[N];
+    float2 t[N], ds[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        pkj[j] = pk[J0 + j];
+        HOWL_OPAQUE_V(pkj[j]);
+        t[j] = v[j].a;
+        HOWL_OPAQUE_V(t[j].x);
+        HOWL_OPAQUE_V(t[j].y);
+        ds[j] = make_float2(0.0f, 0.0f);
+    }
     if (MODE == 0) {
-        // stored activations are non-negative (sums of ReLU outputs); layers with a residual add keep the ReLU mask of
-        // their own convolution in the sign bit (conv_epilogue), hence the fabs
-        v0 = fabsf(v0);
-        v1 = fabsf(v1);
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            // stored activations are non-negative (sums of ReLU outputs); layers with a residual add keep the ReLU mask of
+            // their own convolution in the sign bit (conv_epilogue), hence the fabs
+            t[j].x = fabsf(t[j].x);
+            t[j].y = fabsf(t[j].y);
+        }
         if (cfg.affine) {   // xhat = (|s| - mean) * rstd as one fused multiply-add: lm = [-mean * rstd | rstd]
-            const float sh = lm[c], r = lm[CP + c];
-            v0 = fmaf(v0, r, sh);
-            v1 = fmaf(v1, r, sh);
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                const int c = (pkj[j] >> 20) & 0x3F;
+                const float sh = lm[c], r = lm[CP + c];
+                t[j].x = fmaf(t[j].x, r, sh);
+                t[j].y = fmaf(t[j].y, r, sh);
+            }
         }
     } else if (cfg.fused) {
-        float2 ds, dz;
-        bn_relu_bwd_pair(v, lm + c, cfg.even, ds, dz);
-        if (cfg.ds != nullptr)
-            *reinterpret_cast<float2*>(reinterpret_cast<char*>(cfg.ds + base) + 8u * (unsigned)i2) = ds;
-        v0 = dz.x;
-        v1 = dz.y;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            SlotVal w = v[j];
+            w.a = t[j];
+            bn_relu_bwd_pair(w, lm + ((pkj[j] >> 20) & 0x3F), cfg.even, ds[j], t[j]);
+        }
     }
-    if (zero) v0 = v1 = 0.0f;
-    float* d = tile + (pkj & 0xFFFFF);
-    d[0] = v0;
-    d[1] = v1;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        if (pkj[j] >= 0) {
+            const bool zero = (zmask >> (J0 + j)) & 1u;
+            float* d = tile + (pkj[j] & 0xFFFFF);
+            d[0] = zero ? 0.0f : t[j].x;
+            d[1] = zero ? 0.0f : t[j].y;
+        }
+    }
+    if (MODE == 1 && cfg.fused && cfg.ds != nullptr) {
+        char* dsb = reinterpret_cast<char*>(cfg.ds + base);
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            unsigned off = 8u * (unsigned)(tid + (J0 + j) * CONV_THREADS);
+            HOWL_OPAQUE_V(off);
+            if (pkj[j] >= 0) *reinterpret_cast<float2*>(dsb + off) = ds[j];
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -598,6 +639,8 @@ __device__ __forceinline__ void conv_epilogue(const f32x4 (&acc)[NTW], const flo
     const EpiAddr<NTW, TS> ea(e, t0, lane);
     constexpr int ts = TS;
     char* obase = reinterpret_cast<char*>(e.out + ubase);
+    unsigned boff = ea.boff;      // made here, per utterance: hoisted out of the utterance loop the lane offset becomes a 64-bit
+    HOWL_OPAQUE_V(boff);          // address per store, and one of those pairs a spill that is reloaded in front of the stores
     float u0 = 0.0f, u1 = 0.0f;      // this utterance's share of the two statistics sums
 #pragma unroll
     for (int i = 0; i < NTW; ++i) {
@@ -637,7 +680,7 @@ __device__ __forceinline__ void conv_epilogue(const f32x4 (&acc)[NTW], const flo
                         u1 += v0 * fmaf(fabsf(sv.x), e.xrstd, e.xshift) + v1 * fmaf(fabsf(sv.y), e.xrstd, e.xshift);
                     }
                 }
-                *reinterpret_cast<float2*>(obase + (ea.boff + ea.tstep * i + 8u * hh)) = make_float2(v0, v1);
+                *reinterpret_cast<float2*>(obase + (boff + ea.tstep * i + 8u * hh)) = make_float2(v0, v1);
             }
         }
     }
@@ -721,8 +764,7 @@ __device__ __forceinline__ void conv_loop(const ConvLoop& c, const ConvEpilogue&
         if constexpr (NTW > 0) k_run<NTW>(k, acc, c.CS, a0);
         HOWL_WINO_BAR();
         if constexpr (STAGE) {
-            slot_write<MODE>(v[0], cfg, ubase + r1, tid, pk1[0], c.tile, c.lm, HALO == 2 && zb && ((gx.pad[1] >> 0) & 1));
-            slot_write<MODE>(v[1], cfg, ubase + r1, tid + CONV_THREADS, pk1[1], c.tile, c.lm, HALO == 2 && zb && ((gx.pad[1] >> 1) & 1));
+            burst_write<MODE, 2, 0>(v, cfg, ubase + r1, tid, pk1, c.tile, c.lm, HALO == 2 && zb ? gx.pad[1] : 0u);
             if constexpr (HALO == 1) halo_write<MODE>(v[2], cfg, hs[1], lcol, c.tile, c.lm);
             if constexpr (HALO == 2) grid_write<MODE>(ge, cfg, gx, 1, b, P / PW, c.tile, c.lm);
             slot_load<MODE, HALO>(v[0], cfg, ubase + r1, tid + 2 * CONV_THREADS, pk1[2], bsl);
@@ -733,8 +775,7 @@ __device__ __forceinline__ void conv_loop(const ConvLoop& c, const ConvEpilogue&
         if constexpr (NTW > 0) k_run<NTW>(k, acc, c.CS, a1);
         HOWL_WINO_BAR();
         if constexpr (STAGE) {
-            slot_write<MODE>(v[0], cfg, ubase + r1, tid + 2 * CONV_THREADS, pk1[2], c.tile, c.lm, HALO == 2 && zb && ((gx.pad[1] >> 2) & 1));
-            slot_write<MODE>(v[1], cfg, ubase + r1, tid + 3 * CONV_THREADS, pk1[3], c.tile, c.lm, HALO == 2 && zb && ((gx.pad[1] >> 3) & 1));
+            burst_write<MODE, 2, 2>(v, cfg, ubase + r1, tid, pk1, c.tile, c.lm, HALO == 2 && zb ? gx.pad[1] : 0u);
         }
         HOWL_STAIR(1);
         HOWL_WINO_CHUNK();
@@ -755,9 +796,7 @@ __device__ __forceinline__ void conv_loop(const ConvLoop& c, const ConvEpilogue&
         if constexpr (NTW > 0) k_run<NTW>(k, acc, c.CS, b0);
         HOWL_WINO_BAR();
         if (STAGE && more) {
-            slot_write<MODE>(v[0], cfg, nbase, tid, pk0[0], c.tile, c.lm, HALO == 2 && zn && ((gx.pad[0] >> 0) & 1));
-            slot_write<MODE>(v[1], cfg, nbase, tid + CONV_THREADS, pk0[1], c.tile, c.lm, HALO == 2 && zn && ((gx.pad[0] >> 1) & 1));
-            slot_write<MODE>(v[2], cfg, nbase, tid + 2 * CONV_THREADS, pk0[2], c.tile, c.lm, HALO == 2 && zn && ((gx.pad[0] >> 2) & 1));
+            burst_write<MODE, 3, 0>(v, cfg, nbase, tid, pk0, c.tile, c.lm, HALO == 2 && zn ? gx.pad[0] : 0u);
             if constexpr (HALO == 2) grid_write<MODE>(ge, cfg, gx, 0, bn, P / PW, c.tile, c.lm);
             slot_load<MODE, HALO>(v[0], cfg, nbase, tid + 3 * CONV_THREADS, pk0[3], bnsl);
             slot_load<MODE, HALO>(v[1], cfg, nbase, tid + 4 * CONV_THREADS, pk0[4], bnsl);
@@ -768,8 +807,7 @@ __device__ __forceinline__ void conv_loop(const ConvLoop& c, const ConvEpilogue&
         if constexpr (NTW > 0) k_run<NTW>(k, acc, c.CS, b1);
         HOWL_WINO_BAR();
         if (STAGE && more) {
-            slot_write<MODE>(v[0], cfg, nbase, tid + 3 * CONV_THREADS, pk0[3], c.tile, c.lm, HALO == 2 && zn && ((gx.pad[0] >> 3) & 1));
-            slot_write<MODE>(v[1], cfg, nbase, tid + 4 * CONV_THREADS, pk0[4], c.tile, c.lm, HALO == 2 && zn && ((gx.pad[0] >> 4) & 1));
+            burst_write<MODE, 2, 3>(v, cfg, nbase, tid, pk0, c.tile, c.lm, HALO == 2 && zn ? gx.pad[0] : 0u);
             if constexpr (HALO == 1) halo_write<MODE>(v[2], cfg, hs[0], lcol, c.tile, c.lm);
         }
         // the epilogue's operands take the registers the staging slots just released; they land under the last K segment
@@ -969,7 +1007,7 @@ __device__ __forceinline__ void conv3x3_body(
         }
     }
     if (MODE == 0 && !folding && tid < CP) {
-        lm[tid] = cfg.affine ? -in_stats[tid] * in_stats[CP + tid] : 0.0f;     // slot_write: xhat = |s| * rstd + this
+        lm[tid] = cfg.affine ? -in_stats[tid] * in_stats[CP + tid] : 0.0f;     // burst_write: xhat = |s| * rstd + this
         lm[CP + tid] = cfg.affine ? in_stats[CP + tid] : 1.0f;
     }
     const int cout = 16 * nt + (lane & 15);
@@ -984,10 +1022,8 @@ __device__ __forceinline__ void conv3x3_body(
                            pool, 4 * slices, t0};
     __syncthreads();  // weights, zero fill and the per-channel constants visible before the first stage
     if (b < B) {
-#pragma unroll
-        for (int j = 0; j < NS0; ++j)
-            slot_write<MODE>(first[j], cfg, (size_t)b * NMAP * P, tid + j * CONV_THREADS, pk0[j], tile, lm,
-                             HALO == 2 && strip_pos(sg, b, H).hv < H && ((gx.pad[0] >> j) & 1));
+        burst_write<MODE, NS0, 0>(first, cfg, (size_t)b * NMAP * P, tid, pk0, tile, lm,
+                                  HALO == 2 && strip_pos(sg, b, H).hv < H ? gx.pad[0] : 0u);
         if constexpr (HALO == 1) halo_write<MODE>(firsth, cfg, hs[0], (b & 1) ? 0 : WP - 1, tile, lm);
         if constexpr (HALO == 2) grid_write<MODE>(firstg, cfg, gx, 0, b, H, tile, lm);
     }
@@ -1109,7 +1145,7 @@ __global__ __launch_bounds__(CONV_THREADS) void conv3x3_mfma_kernel(StageCfg cfg
 // ds_read_b32 is served per 32-lane half over 32 banks; a half holds {channels 0..15} x {groups g, g+1}: conflict-free iff the
 // channel stride is = 2 (mod 32) (all even banks) and the two groups' rows are an odd number of floats apart (pitches 11, 13).
 // With HOWL_RES8_BWD_FUSED (default) dz_i is built on the way into LDS from (dx_i, s_i, dskip) exactly as the data gradient's
-// staging does (slot_write<1>): neither role of the pair reads a dz tensor.
+// staging does (burst_write<1>): neither role of the pair reads a dz tensor.
 constexpr int WPZ = 11;
 constexpr int WNT = 4, WNB = 5;   // staging slots per thread: top regions (<= 13 rows x 45 ch / 2 / 768), bottom regions (<= 16 rows)
 __host__ __device__ inline int wgrad_r1(int H) { return wgrad_rounds(H) / 2; }
@@ -1226,7 +1262,7 @@ struct WSlot {
     float2 x;
 };
 
-// z slot: the data gradient's staging arithmetic (slot_write<1>) with this kernel's addressing; addresses are "uniform base +
+// z slot: the data gradient's staging arithmetic (burst_write<1>) with this kernel's addressing; addresses are "uniform base +
 // 32-bit lane offset" recomputed from the packed descriptor where they are used
 template <int HALO = 0>
 __device__ __forceinline__ void wz_load(SlotVal& v, const StageCfg& cfg, size_t ubase, int pkj, int chj, int b) {
