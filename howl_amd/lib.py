@@ -188,6 +188,14 @@ DECIDE_SIGNATURES = {
 }
 DECIDE_SIZE_FUNCS = {"howl_decide_supported": [POINTER(HowlDecideConfig), c_int]}
 
+# The long-target CTC entry points of ``include/howl_hip_ctc_long.h`` (their own tables again: ``tests/test_emu_ctc_long.py`` checks
+# them against that header); ``howl_ctc_loss_long`` takes ``howl_ctc_loss``'s argument list
+CTC_LONG_SIGNATURES = {
+    "howl_ctc_loss_long": list(SIGNATURES["howl_ctc_loss"]),
+}
+CTC_LONG_SIZE_FUNCS = {"howl_ctc_long_supported": [c_int, c_int, c_int], "howl_ctc_long_window_rows": [c_int],
+                       "howl_ctc_long_workspace_floats": [c_int, c_int, c_int]}
+
 
 class HowlHipError(RuntimeError):
     pass
@@ -204,11 +212,13 @@ class Library:
         self.cdll = ctypes.CDLL(str(path))
         self.cdll.howl_last_error.restype = c_char_p
         self.cdll.howl_last_error.argtypes = []
-        for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES, **LSTM_STREAM_SIGNATURES, **DECIDE_SIGNATURES}.items():
+        for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES, **LSTM_STREAM_SIGNATURES, **DECIDE_SIGNATURES,
+                               **CTC_LONG_SIGNATURES}.items():
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = c_int
             fn.argtypes = argtypes
-        for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS, **LSTM_STREAM_SIZE_FUNCS, **DECIDE_SIZE_FUNCS}.items():
+        for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS, **LSTM_STREAM_SIZE_FUNCS, **DECIDE_SIZE_FUNCS,
+                               **CTC_LONG_SIZE_FUNCS}.items():
             fn = getattr(self.cdll, name)
             fn.restype = c_size_t
             fn.argtypes = argtypes

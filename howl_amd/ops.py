@@ -168,7 +168,7 @@ def xent(logits, labels, want_grad=True):
     return loss, dlogits
 
 
-def _ctc_launch(scores, targets, input_lengths, target_lengths, blank, max_target, want_grad, defer_mean=False):
+def _ctc_launch(scores, targets, input_lengths, target_lengths, blank, max_target, want_grad, defer_mean=False, long_targets=False):
     T, B, C = scores.shape
     dev = scores.device
     # the gradient takes the memory layout of the model's (B, T, C) output buffer, handed back as a (T, B, C) view
@@ -177,9 +177,14 @@ def _ctc_launch(scores, targets, input_lengths, target_lengths, blank, max_targe
     loss = torch.empty((), dtype=torch.float32, device=dev)
     vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())     # strided views: strides are passed explicitly
     # whole clips (more than 128 frames): the alpha rows of the windows behind the last one wait in a workspace
-    ws_floats = int(_lib.get().cdll.howl_ctc_workspace_floats(T, B)) if want_grad else 0
+    # (long_targets: howl_ctc_loss_long, include/howl_hip_ctc_long.h -- the window and the row width depend on the longest target)
+    if long_targets:
+        _ctc_long_check(T, C, max_target)
+        ws_floats = int(_lib.get().cdll.howl_ctc_long_workspace_floats(T, B, max_target)) if want_grad else 0
+    else:
+        ws_floats = int(_lib.get().cdll.howl_ctc_workspace_floats(T, B)) if want_grad else 0
     ws = torch.empty(ws_floats, dtype=torch.float32, device=dev) if ws_floats else None
-    _lib.get().call("howl_ctc_loss", vp(scores), scores.stride(0), scores.stride(1), T, B, C, vp(targets),
+    _lib.get().call("howl_ctc_loss_long" if long_targets else "howl_ctc_loss", vp(scores), scores.stride(0), scores.stride(1), T, B, C, vp(targets),
                     targets.stride(0), max_target, _p(input_lengths, torch.int64), _p(target_lengths, torch.int64), blank,
                     _p(nll), None if defer_mean else _p(loss), vp(dlogits), 0 if dlogits is None else dlogits.stride(0),
                     0 if dlogits is None else dlogits.stride(1), vp(ws), ws_floats, _stream())
@@ -193,16 +198,16 @@ class _CtcLoss(torch.autograd.Function):
     kernel returns the loss and d loss / d scores in one pass (``howl_ctc_loss``)."""
 
     @staticmethod
-    def forward(ctx, scores, targets, input_lengths, target_lengths, blank, max_target):
+    def forward(ctx, scores, targets, input_lengths, target_lengths, blank, max_target, long_targets=False):
         loss, dlogits = _ctc_launch(scores, targets, input_lengths, target_lengths, blank, max_target,
-                                    ctx.needs_input_grad[0])
+                                    ctx.needs_input_grad[0], long_targets=long_targets)
         ctx.save_for_backward(dlogits)
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
         (dlogits,) = ctx.saved_tensors
-        return dlogits * grad_out, None, None, None, None, None
+        return dlogits * grad_out, None, None, None, None, None, None
 
 
 def _ctc_args(scores, targets, input_lengths, target_lengths, max_target):
@@ -226,34 +231,53 @@ def ctc_supported(T: int, C: int, max_target: int) -> bool:
     return bool(_lib.get().cdll.howl_ctc_supported(int(T), int(C), int(max_target)))
 
 
-def ctc_loss_fwd_bwd(scores, targets, input_lengths, target_lengths, blank: int, max_target=None, defer_mean=False):
+CTC_LONG_MAX_LABELS = 255      # HOWL_CTC_LONG_MAX_LABELS
+
+
+def ctc_long_supported(T: int, C: int, max_target: int) -> bool:
+    """``howl_ctc_long_supported``: the range of ``ctc_loss(..., long_targets=True)``."""
+    return bool(_lib.get().cdll.howl_ctc_long_supported(int(T), int(C), int(max_target)))
+
+
+def _ctc_long_check(T, C, max_target):
+    if not ctc_long_supported(T, C, max_target):
+        raise _lib.HowlHipError(f"ctc_loss: T={T} frames, C={C} classes, the batch's longest target has {max_target} labels: outside "
+                                f"howl_ctc_loss_long's range (T <= 8192, C <= 64, targets <= {CTC_LONG_MAX_LABELS} labels)")
+
+
+def ctc_loss_fwd_bwd(scores, targets, input_lengths, target_lengths, blank: int, max_target=None, defer_mean=False,
+                     long_targets: bool = False):
     """Loss and d loss / d scores without an autograd graph (training.fused.FusedTrainer.step_sequence): same kernel as
     ``ctc_loss``; the batch must be inside the kernel's range.  ``defer_mean``: returns (loss, dscores, nll, target_lengths)
     with ``loss`` still unwritten -- the batch mean is left to ``howl_head_bwd`` (``SequentialLstm._launch_backward(...,
-    ctc_mean=(nll, target_lengths, loss))``), one launch fewer."""
+    ctc_mean=(nll, target_lengths, loss))``), one launch fewer.  ``long_targets``: as for ``ctc_loss``."""
     targets, input_lengths, target_lengths, max_target = _ctc_args(scores, targets, input_lengths, target_lengths, max_target)
     if scores.stride(2) != 1 or scores.dtype != torch.float32:
         raise ValueError("ctc_loss_fwd_bwd: scores must be fp32 with unit stride over the classes")
-    out = _ctc_launch(scores, targets, input_lengths, target_lengths, int(blank), max_target, True, defer_mean)
+    out = _ctc_launch(scores, targets, input_lengths, target_lengths, int(blank), max_target, True, defer_mean, long_targets)
     return out + (target_lengths,) if defer_mean else out
 
 
-def ctc_loss(scores, targets, input_lengths, target_lengths, blank: int):
+def ctc_loss(scores, targets, input_lengths, target_lengths, blank: int, long_targets: bool = False):
     """``nn.CTCLoss(blank)(torch.log_softmax(scores, -1), targets, input_lengths, target_lengths)`` of the reference's training
     loop (train.py:250-256, 291-296) for ``scores`` of shape (T, B, C) on the device, as ONE fused kernel.  ``targets`` is the
     padded (B, L) int64 matrix; the two length vectors may live on the host (as in the reference) or on the device.  Whole
     clips are inside the kernel's range (T <= 8192 frames, walked in 128-frame windows); a batch outside it (C > 64, a
-    target longer than 31 labels, scores that are not fp32) raises -- the training path has no vendor fallback."""
+    target longer than 31 labels -- 255 with ``long_targets=True``, scores that are not fp32) raises -- the training path has no
+    vendor fallback.  ``long_targets=True`` takes ``howl_ctc_loss_long`` (include/howl_hip_ctc_long.h): the same bits for a batch
+    of at most 31 labels, and 2, 4 or 8 states of the label sequence per lane beyond (up to 63, 127, 255 labels)."""
     targets_d, in_d, tl_d, max_target = _ctc_args(scores, targets, input_lengths, target_lengths, None)
     T, B, C = scores.shape
     if scores.dtype != torch.float32:
         raise _lib.HowlHipError(f"ctc_loss: scores must be fp32 (got {scores.dtype})")
-    if not _lib.get().cdll.howl_ctc_supported(T, C, max_target):
+    if long_targets:
+        _ctc_long_check(T, C, max_target)
+    elif not _lib.get().cdll.howl_ctc_supported(T, C, max_target):
         raise _lib.HowlHipError(f"ctc_loss: T={T} frames, C={C} classes, targets of {max_target} labels: outside howl_ctc_loss's "
                                 "range (T <= 8192, C <= 64, targets <= 31)")
     if scores.stride(2) != 1:
         scores = scores.contiguous()
-    return _CtcLoss.apply(scores, targets_d, in_d, tl_d, int(blank), max_target)
+    return _CtcLoss.apply(scores, targets_d, in_d, tl_d, int(blank), max_target, bool(long_targets))
 
 
 def adamw_step(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=1.0):

@@ -185,12 +185,13 @@ class FusedTrainer:
             self.model._launch_backward(None, out_grads=self.fp.grad_views, ctc_mean=(self.model.ctc_nll, kw["ctc"][1], loss), adamw=adamw)
             return self._finish_sequence_step(scores, loss)
         # log-softmax + CTC + their backward as one launch at any clip length (128-frame windows beyond 128 frames); the batch
-        # mean of the loss rides in the head's backward launch (HowlCtcMean).  Outside the kernel's range (C > 64, a target
-        # of more than 31 labels, T > 8192): HowlHipError from the library -- no vendor kernels on the training path
+        # mean of the loss rides in the head's backward launch (HowlCtcMean).  Targets beyond 31 labels take the long-target bodies
+        # of howl_ctc_loss_long (same bits up to 31).  Outside the kernel's range (C > 64, a target of more than 255 labels,
+        # T > 8192): HowlHipError naming the batch's longest target -- no vendor kernels on the training path
         if "ctc" in kw:      # (already on the device for the fused launch's benefit: no second upload)
             targets, target_lengths = kw["ctc"][0], kw["ctc"][1]
         loss, dscores, nll, tl_dev = ops.ctc_loss_fwd_bwd(scores, targets, frame_lengths, target_lengths, blank, max_target,
-                                                          defer_mean=True)
+                                                          defer_mean=True, long_targets=True)
         ctc_mean = (nll, tl_dev, loss)
         # single replica: nothing sits between the backward's gradient fold and the optimiser, so the step rides in the fold
         # (howl_seq_lstm_bwd's HowlAdamW: one launch and one pass over the gradients fewer)

@@ -263,7 +263,7 @@ def main(argv=None):
                 else:
                     scores = model(feats, frame_lengths)
                     optimizer.zero_grad()
-                    loss = ops.ctc_loss(scores, batch.labels, frame_lengths, batch.label_lengths, ctx.blank_label)
+                    loss = ops.ctc_loss(scores, batch.labels, frame_lengths, batch.label_lengths, ctx.blank_label, long_targets=True)
                     loss.backward()
                     optimizer.step()
             total_loss += loss.detach().reshape(())                       # accumulated on the device (train.py:303-304)

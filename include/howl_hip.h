@@ -268,7 +268,9 @@ int howl_xent_fwd_bwd(const float* logits, const long long* labels, int B, int C
  * input_lengths[b] >= 0 (an input length above T counts as T).  Rows of targets hold max_target_length labels: tgt_stride >=
  * max_target_length when B > 1.  An utterance outside the contract gets nll[b] = +inf (so loss = +inf) and all-zero dlogits
  * rows; only its targets[b][0, max_target_length) are read, and every other utterance's nll and dlogits rows are the bits that
- * batch gives with that utterance made valid. */
+ * batch gives with that utterance made valid.
+ * Targets of 32 .. 255 labels: howl_ctc_loss_long in howl_hip_ctc_long.h (same arguments, same contract, and the same bits as this
+ * entry for a batch inside this entry's range). */
 int howl_ctc_supported(int T, int C, int max_target_length);
 size_t howl_ctc_workspace_floats(int T, int B);
 int howl_ctc_loss(const float* logits, long st_t, long st_b, int T, int B, int C, const long long* targets, long tgt_stride,
