@@ -89,6 +89,20 @@ class HowlMbWsLayer(ctypes.Structure):
                                      "nslab", "group_rows")]
 
 
+class HowlGruParams(ctypes.Structure):
+    """``HowlGruParams`` / ``HowlGruGrads`` of ``include/howl_hip_gru.h``: the sixteen tensors in ``state_dict`` order."""
+    _fields_ = [(n, P) for n in ("conv1_w", "conv1_b", "bn1_w", "bn1_b", "conv2_w", "conv2_b", "bn2_w", "bn2_b", "w_ih", "w_hh", "b_ih",
+                                 "b_hh", "w1", "b1", "w2", "b2")]
+
+
+class HowlGruGrads(ctypes.Structure):
+    _fields_ = list(HowlGruParams._fields_)
+
+
+class HowlGruBuffers(ctypes.Structure):
+    _fields_ = [(n, P) for n in ("bn1_mean", "bn1_var", "bn1_batches", "bn2_mean", "bn2_var", "bn2_batches")]
+
+
 class HowlDecideConfig(ctypes.Structure):
     """``HowlDecideConfig`` of ``include/howl_hip_decide.h``: a host struct; ``weights`` / ``color`` are device pointers."""
     _fields_ = [("mode", c_int), ("C", c_int), ("blank", c_int), ("negative", c_int), ("threshold", c_double), ("smoothing_ms", c_double),
@@ -196,6 +210,16 @@ CTC_LONG_SIGNATURES = {
 CTC_LONG_SIZE_FUNCS = {"howl_ctc_long_supported": [c_int, c_int, c_int], "howl_ctc_long_window_rows": [c_int],
                        "howl_ctc_long_workspace_floats": [c_int, c_int, c_int]}
 
+# The gru model's entry points of ``include/howl_hip_gru.h`` (their own tables again: ``tests/test_emu_gru.py`` checks them
+# against that header)
+GRU_SIGNATURES = {
+    "howl_gru_fwd": [POINTER(HowlGruParams), POINTER(HowlGruBuffers), P, c_long, c_long, c_long, c_int, c_int, c_int, c_int, P, c_int, P,
+                     c_float, P, P, c_size_t, STREAM],
+    "howl_gru_bwd": [POINTER(HowlGruParams), P, c_long, c_long, c_long, c_int, c_int, c_int, c_int, P, c_float, P, POINTER(HowlGruGrads),
+                     P, c_size_t, STREAM],
+}
+GRU_SIZE_FUNCS = {"howl_gru_supported": [c_int, c_int, c_int, c_int], "howl_gru_workspace_bytes": [c_int, c_int]}
+
 
 class HowlHipError(RuntimeError):
     pass
@@ -213,12 +237,12 @@ class Library:
         self.cdll.howl_last_error.restype = c_char_p
         self.cdll.howl_last_error.argtypes = []
         for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES, **LSTM_STREAM_SIGNATURES, **DECIDE_SIGNATURES,
-                               **CTC_LONG_SIGNATURES}.items():
+                               **CTC_LONG_SIGNATURES, **GRU_SIGNATURES}.items():
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = c_int
             fn.argtypes = argtypes
         for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS, **LSTM_STREAM_SIZE_FUNCS, **DECIDE_SIZE_FUNCS,
-                               **CTC_LONG_SIZE_FUNCS}.items():
+                               **CTC_LONG_SIZE_FUNCS, **GRU_SIZE_FUNCS}.items():
             fn = getattr(self.cdll, name)
             fn.restype = c_size_t
             fn.argtypes = argtypes

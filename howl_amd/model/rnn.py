@@ -1,5 +1,6 @@
 """``SequentialLstm`` ("seq-lstm") and ``SimpleLstm`` ("lstm") of ``howl/model/rnn.py:41-91`` on MI355X kernels
-(``howl_amd/csrc/lstm.hip``): packed-sequence LSTM(40 -> 128) + Linear(128,256)-ReLU-Linear(256,C).
+(``howl_amd/csrc/lstm.hip``): packed-sequence LSTM(40 -> 128) + Linear(128,256)-ReLU-Linear(256,C); ``SimpleGru`` ("gru") of
+``howl/model/rnn.py:94-130`` on ``howl_amd/csrc/gru.hip``: conv encoder + GRU(40 -> 96) + Linear-ReLU-Dropout-Linear.
 
 Same construction order / ``state_dict`` keys (``lstm.weight_ih_l0 ...``, ``dnn.0.*``, ``dnn.2.*``), same call protocol
 ``model(x: (B, C>=1, M, T), lengths)`` and streaming-state protocol as the reference; ``nn.LSTM`` / ``nn.Linear`` are
@@ -12,12 +13,12 @@ import torch
 import torch.nn as nn
 
 from howl_amd import lib as _lib
-from howl_amd import ops
+from howl_amd import ops, parallel
 from howl_amd.settings import _EnvSettings
 
 from .base import RegisteredModel
 
-__all__ = ["LstmConfig", "LstmStreamSession", "SequentialLstm", "SimpleLstm"]
+__all__ = ["LASEncoderConfig", "LstmConfig", "LstmStreamSession", "SequentialLstm", "SimpleGru", "SimpleLstm"]
 
 HID = 128
 
@@ -26,6 +27,15 @@ class LstmConfig(_EnvSettings):
     num_mels: int = 40
     hidden_size: int = 128
     num_labels: int = 2
+
+
+class LASEncoderConfig(_EnvSettings):
+    num_mels: int = 40
+    num_spec_channels: int = 3
+    num_latent_channels: int = 8
+    hidden_size: int = 96
+    num_layers: int = 1
+    use_maxpool: bool = True
 
 
 def _vp(t):
@@ -465,3 +475,144 @@ class SimpleLstm(_LstmBase, name="lstm"):
             # rnn.py:89-90 assigns streaming_state, which the base class setter drops (base.py:35-37): stays stateless
             self.streaming_state = (hT.unsqueeze(0), cT.unsqueeze(0))
         return self._head(hT)
+
+
+class _GruFunction(torch.autograd.Function):
+    """The whole gru model as one differentiable function of its sixteen parameters: ``howl_gru_fwd`` / ``howl_gru_bwd``."""
+
+    @staticmethod
+    def forward(ctx, model, feat, lengths, t_out, *params):
+        logits = model._launch_forward(feat, lengths, t_out)
+        ctx.model, ctx.feat, ctx.saved = model, feat, model._gru_saved
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        ctx.model._gru_saved = ctx.saved
+        grads = ctx.model._launch_backward(ctx.feat, dlogits.contiguous())
+        return (None, None, None, None) + tuple(grads)
+
+
+class SimpleGru(RegisteredModel, name="gru"):
+    """``SimpleGru`` of the reference (rnn.py:94-130) on the kernels of ``howl_amd/csrc/gru.hip``, the whole model one C-ABI call
+    per direction: Conv2d(1,8,3,padding=(1,3)) - BatchNorm - ReLU - MaxPool(1,2) - Conv2d(8,1,3,padding=1) - ReLU - BatchNorm
+    - GRU(40 -> 96) on the packed batch - Linear(96,192) - ReLU - Dropout(0.2) - Linear(192, num_labels) on the final states.
+    Same construction order and ``state_dict`` keys (``conv_encoder.{0,1,4,6}.*``, ``lstm_encoder.*_l0``, ``dnn.{0,3}.*``): a
+    reference workspace loads with ``strict=True``; the ``nn`` modules are parameter containers only.
+
+    The whole (B, 40, T) buffer goes through the encoder, padded frames included (they count in the BatchNorm statistics, as in
+    the reference); utterance b's recurrence runs ``(lengths[b] + 4) // 2`` steps.  Decided once:
+
+    * the reference's ``lengths += 4`` mutates the caller's tensor; this class never writes to ``lengths`` (the entry points
+      hand over a fresh tensor each batch, so nothing observable changes);
+    * like ``pack_padded_sequence``, host ``lengths`` must be sorted in decreasing order (the ``RuntimeError`` of the LSTM
+      models); device-resident lengths together with ``t_out`` are trusted, as there;
+    * ``LASEncoderConfig`` other than ``num_mels=40, num_latent_channels=8, hidden_size=96, use_maxpool=True`` raises
+      ``NotImplementedError`` at construction (``num_spec_channels`` and ``num_layers`` are not used by this model);
+    * dropout draws one ``howl_dropout_mask`` launch per training forward, keyed from torch's CPU generator and salted by the
+      replica rank, unless ``forced_keep_mask`` (B, 192 of 0/1) is set.
+    """
+    NEEDS_LENGTHS = True       # FusedTrainer.step passes the frame lengths through
+
+    def __init__(self, num_labels: int, config: LASEncoderConfig = None):
+        super().__init__(num_labels)
+        config = config or LASEncoderConfig()
+        for name, want in (("num_mels", 40), ("num_latent_channels", 8), ("hidden_size", 96), ("use_maxpool", True)):
+            if getattr(config, name) != want:
+                raise NotImplementedError(f"the MI355X gru kernels are specialised for {name}={want} (got {getattr(config, name)})")
+        conv1 = nn.Conv2d(1, config.num_latent_channels, 3, padding=(1, 3))
+        conv2 = nn.Conv2d(config.num_latent_channels, 1, 3, padding=1)
+        self.conv_encoder = nn.Sequential(conv1, nn.BatchNorm2d(config.num_latent_channels), nn.ReLU(), nn.MaxPool2d((1, 2)), conv2,
+                                          nn.ReLU(), nn.BatchNorm2d(1))
+        self.use_maxpool = config.use_maxpool
+        self.lstm_encoder = nn.GRU(config.num_mels, config.hidden_size, bidirectional=False)
+        self.dnn = nn.Sequential(nn.Linear(config.hidden_size, int(2 * config.hidden_size)), nn.ReLU(), nn.Dropout(0.2),
+                                 nn.Linear(int(2 * config.hidden_size), num_labels))
+        self.dropout_p = 0.2
+        self.forced_keep_mask = None     # tests: (B, 192) 0/1 mask used instead of a fresh draw
+        self._gru_saved = None
+
+    def hot_parameters(self):
+        """Parameters in the library's gradient order (``HowlGruGrads``) = ``state_dict`` order."""
+        e, r, d = self.conv_encoder, self.lstm_encoder, self.dnn
+        return [e[0].weight, e[0].bias, e[1].weight, e[1].bias, e[4].weight, e[4].bias, e[6].weight, e[6].bias, r.weight_ih_l0,
+                r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0, d[0].weight, d[0].bias, d[3].weight, d[3].bias]
+
+    def _inputs(self, x, lengths, t_out):
+        """-> (x0 (B, 40, T) view of the log-Mel channel, device int64 lengths or None).  Host lengths are checked as
+        ``_LstmBase._lstm_inputs`` checks them; device lengths with ``t_out`` (their maximum) are trusted."""
+        x0 = x[:, 0]
+        if not ops.on_device(x0):
+            raise _lib.HowlHipError("gru input must be on a HIP device (no CPU fallback)")
+        B, _, T = x0.shape
+        if lengths is not None and t_out is not None and ops.on_device(lengths):
+            if lengths.numel() != B or not 1 <= t_out <= T:
+                raise RuntimeError("lengths must have one entry per sequence and t_out must be in 1..T")
+            lengths = lengths.to(torch.int64)
+        elif lengths is not None:
+            lc = lengths.detach().cpu().long()
+            if lc.numel() != B:
+                raise RuntimeError("lengths must have one entry per sequence")
+            if (lc[:-1] < lc[1:]).any():
+                raise RuntimeError("`lengths` array must be sorted in decreasing order (pack_padded_sequence semantics)")
+            if lc.min() <= 0 or lc.max() > T:
+                raise RuntimeError("lengths must be in 1..T")
+            lengths = lc.to(x0.device)
+        return x0, lengths
+
+    def _draw_mask(self, B, device):
+        if self.forced_keep_mask is not None:
+            return self.forced_keep_mask.to(device=device, dtype=torch.float32).contiguous()
+        if self.dropout_p <= 0:
+            return None
+        # one launch of the counter-based device generator; the key comes from torch's CPU generator (a host draw: reproducible
+        # under torch.manual_seed, nothing read back from the device)
+        mask = torch.empty((B, 192), dtype=torch.float32, device=device)
+        key = int(torch.randint(0, 2 ** 62, (1,)).item())
+        key ^= (parallel.world_info()[0] * 0x9E3779B97F4A7C15) & (2 ** 62 - 1)   # replicas share the CPU seed, not the mask
+        _lib.get().call("howl_dropout_mask", _vp(mask), mask.numel(), float(self.dropout_p), ctypes.c_ulonglong(key), ops._stream())
+        return mask
+
+    def _launch_forward(self, feat, lengths, t_out=None):
+        """feat (B, C>=1, 40, T), frame lengths (or None = all T) -> logits (B, num_labels); in training mode keeps what
+        ``_launch_backward`` needs (the library's workspace)."""
+        x0, lengths = self._inputs(feat, lengths, t_out)
+        B, M, T = x0.shape
+        cdll = _lib.get().cdll
+        if not cdll.howl_gru_supported(B, M, T, self.num_labels):
+            raise _lib.HowlHipError(f"gru: B={B}, {M} mel bins, T={T}, {self.num_labels} labels is outside the kernels' range "
+                                    f"(40 mel bins, 1..8192 frames, 1..64 labels)")
+        ps = self.hot_parameters()
+        e = self.conv_encoder
+        prm = _lib.HowlGruParams(*[_vp(p) for p in ps])
+        buf = _lib.HowlGruBuffers(_vp(e[1].running_mean), _vp(e[1].running_var), _vp(e[1].num_batches_tracked), _vp(e[6].running_mean),
+                                  _vp(e[6].running_var), _vp(e[6].num_batches_tracked))
+        ws = torch.empty(cdll.howl_gru_workspace_bytes(B, T), dtype=torch.uint8, device=x0.device)
+        logits = torch.empty((B, self.num_labels), dtype=torch.float32, device=x0.device)
+        mask = self._draw_mask(B, x0.device) if self.training else None
+        if mask is not None and tuple(mask.shape) != (B, 192):
+            raise RuntimeError(f"forced_keep_mask must be ({B}, 192), got {tuple(mask.shape)}")
+        scale = 1.0 / (1.0 - self.dropout_p) if mask is not None else 1.0
+        _lib.get().call("howl_gru_fwd", ctypes.byref(prm), ctypes.byref(buf), _vp(x0), x0.stride(0), x0.stride(1), x0.stride(2), B, M, T,
+                        self.num_labels, _vp(lengths), int(self.training), _vp(mask), scale, _vp(logits), _vp(ws), ws.numel(),
+                        ops._stream())
+        self._gru_saved = (x0, lengths, scale, ws, mask) if self.training else None
+        return logits
+
+    def _launch_backward(self, feat, dlogits, out_grads=None):
+        if self._gru_saved is None:
+            raise NotImplementedError("gru: the backward pass needs a training-mode forward (eval mode saves nothing)")
+        x0, lengths, scale, ws, _ = self._gru_saved
+        B, M, T = x0.shape
+        ps = self.hot_parameters()
+        grads = out_grads if out_grads is not None else [torch.empty_like(p) for p in ps]
+        prm = _lib.HowlGruParams(*[_vp(p) for p in ps])
+        gr = _lib.HowlGruGrads(*[_vp(g) for g in grads])
+        dlogits = dlogits.contiguous()
+        _lib.get().call("howl_gru_bwd", ctypes.byref(prm), _vp(x0), x0.stride(0), x0.stride(1), x0.stride(2), B, M, T, self.num_labels,
+                        _vp(lengths), scale, _vp(dlogits), ctypes.byref(gr), _vp(ws), ws.numel(), ops._stream())
+        self._gru_saved = None
+        return grads
+
+    def forward(self, x, lengths):
+        return _GruFunction.apply(self, x, lengths, None, *self.hot_parameters())

@@ -1,5 +1,5 @@
 """Fused training step: frontend -> forward -> loss -> backward -> (RCCL all-reduce) -> AdamW.  Frame objective
-(res8, mobilenet: cross-entropy) and sequence objective (seq-lstm: log_softmax + CTC).
+(res8, mobilenet, lstm, gru: cross-entropy) and sequence objective (seq-lstm: log_softmax + CTC).
 
 This is the loop body of ``training/run/pretrain_gsc.py:124-133`` / ``training/run/train.py:286-302`` with every
 stage a C-ABI call on the current HIP stream, gradients written straight into one flat fp32 buffer (the unit of the
@@ -39,8 +39,8 @@ class FlatParams:
 
 class FusedTrainer:
     """Works with any model that exposes ``hot_parameters()`` (flat-buffer order), ``_launch_forward(feat)`` and
-    ``_launch_backward(feat, dlogits, out_grads=views)``: ``Res8``, ``MobileNetClassifier`` and ``SimpleLstm`` (``step``; the
-    latter with frame lengths), and with ``SequentialLstm`` (``step_sequence``: ``_launch_forward(feat, lengths)`` /
+    ``_launch_backward(feat, dlogits, out_grads=views)``: ``Res8``, ``MobileNetClassifier``, ``SimpleLstm`` and ``SimpleGru`` (``step``; the
+    latter two with frame lengths), and with ``SequentialLstm`` (``step_sequence``: ``_launch_forward(feat, lengths)`` /
     ``_launch_backward(dscores, out_grads)``).  With more than one rank the flat gradient is summed over RCCL before the
     fused AdamW (which applies 1/world); res8 overlaps that all-reduce with the tail of its backward pass."""
 
@@ -81,7 +81,7 @@ class FusedTrainer:
         return self.step_on_features(feat, labels, lengths, max_frames)
 
     def step_on_features(self, feat, labels, lengths=None, max_frames=None):
-        """``lengths`` / ``max_frames``: frame counts for models that pack their input (``SimpleLstm``); ignored otherwise."""
+        """``lengths`` / ``max_frames``: frame counts for models that pack their input (``SimpleLstm``, ``SimpleGru``); ignored otherwise."""
         bwd_kw = {}
         fused_xent = hasattr(self.model, "_launch_forward_xent") and self.model.num_labels <= self.model.XENT_MAX_LABELS
         if fused_xent:     # res8: the loss rides in the forward's last launch and the backward's second (two launches fewer)

@@ -148,7 +148,7 @@ def main(argv=None):
     workspace.save_settings(SETTINGS)
     writer.add_scalar("Meta/Parameters", sum(p.numel() for p in params))
     if not hasattr(model, "hot_parameters"):
-        raise NotImplementedError(f"{args.model}: no fused MI355X training step (res8, mobilenet, lstm have one)")
+        raise NotImplementedError(f"{args.model}: no fused MI355X training step (res8, mobilenet, lstm, gru have one)")
     trainer = FusedTrainer(model, std_transform, zmuv_transform, SETTINGS.training.learning_rate,
                            weight_decay=SETTINGS.training.weight_decay)
     trainer.broadcast_parameters()                                     # rank 0's initial weights and BatchNorm buffers

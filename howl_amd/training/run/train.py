@@ -207,7 +207,7 @@ def main(argv=None):
     ws.write_args(args)
     ws.save_settings(SETTINGS)
     params = [p for p in model.parameters() if p.requires_grad]
-    fused = (use_frame and args.model in ("res8", "mobilenet", "lstm")) or (not use_frame and args.model == "seq-lstm")
+    fused = (use_frame and args.model in ("res8", "mobilenet", "lstm", "gru")) or (not use_frame and args.model == "seq-lstm")
     needs_lengths = getattr(model, "NEEDS_LENGTHS", False)
     if fused:
         trainer = FusedTrainer(model, std_transform, zmuv_transform, SETTINGS.training.learning_rate,
@@ -215,7 +215,7 @@ def main(argv=None):
         trainer.broadcast_parameters()                             # rank 0's initial weights and BatchNorm buffers
     elif world > 1:
         raise NotImplementedError(f"{args.model} with the {'frame' if use_frame else 'ctc'} objective has no fused step: "
-                                  "data-parallel training needs one (res8 / mobilenet / lstm: frame, seq-lstm: ctc)")
+                                  "data-parallel training needs one (res8 / mobilenet / lstm / gru: frame, seq-lstm: ctc)")
     else:
         optimizer = torch.optim.AdamW(params, SETTINGS.training.learning_rate, weight_decay=SETTINGS.training.weight_decay)
     criterion = torch.nn.CrossEntropyLoss()                        # frame objective; the CTC objective is ops.ctc_loss below
