@@ -179,13 +179,21 @@ class StandardAudioTransform(AugmentModule):
 
     # -- fused fast path ------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def log_mel_for_model(self, audio: torch.Tensor, zmuv) -> torch.Tensor:
+    def log_mel_for_model(self, audio: torch.Tensor, zmuv, channels: int = 1) -> torch.Tensor:
         """ZMUV-normalised log-mels as a (B, 1, M, T) *view* of a (B, T, M) buffer -- the layout res8 / the LSTMs
         read directly.  Same RNG protocol as ``forward`` (one draw per call, VTLP when training and < 0.75).
-        Equivalent to ``zmuv(self(audio))[:, :1]`` without materialising deltas or a permute."""
+        Equivalent to ``zmuv(self(audio))[:, :1]`` without materialising deltas or a permute.
+
+        ``channels=3`` (a model's ``FEATURE_CHANNELS``: las reads log-mels, deltas and accelerations): the contiguous
+        (B, 3, M, T) ``zmuv(self(audio))``, bit for bit, as two launches -- the log-mel launch and the deltas launch with the
+        ZMUV pair in its epilogue -- with the same one draw."""
+        if channels not in (1, 3):
+            raise ValueError(f"log_mel_for_model: channels must be 1 or 3 (got {channels})")
         param = self.augment_params[0]
         use_vtlp = param.enabled and self.rand.random() < param.prob and self.training
         fbp = self._vtlp_fb() if use_vtlp else self._standard_fb()
+        if channels == 3:
+            return ops.deltas(ops.logmel(audio, fbp, self.n_mels, None, layout=0), zmuv.pair() if zmuv is not None else None)
         feat = ops.logmel(audio, fbp, self.n_mels, zmuv.pair() if zmuv is not None else None, layout=1)
         return feat.permute(0, 2, 1).unsqueeze(1)
 

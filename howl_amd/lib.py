@@ -103,6 +103,20 @@ class HowlGruBuffers(ctypes.Structure):
     _fields_ = [(n, P) for n in ("bn1_mean", "bn1_var", "bn1_batches", "bn2_mean", "bn2_var", "bn2_batches")]
 
 
+class HowlLasParams(ctypes.Structure):
+    """``HowlLasParams`` / ``HowlLasGrads`` of ``include/howl_hip_las.h``: the twenty-five distinct tensors in ``state_dict`` order."""
+    _fields_ = [(n, P) for n in ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "bn1_w", "bn1_b", "bn2_w", "bn2_b", "w_ih_f", "w_hh_f", "b_ih_f",
+                                 "b_hh_f", "w_ih_r", "w_hh_r", "b_ih_r", "b_hh_r", "cv", "v_w", "v_b", "k_w", "k_b", "w1", "b1", "w2", "b2")]
+
+
+class HowlLasGrads(ctypes.Structure):
+    _fields_ = list(HowlLasParams._fields_)
+
+
+class HowlLasBuffers(ctypes.Structure):
+    _fields_ = [(n, P) for n in ("bn1_mean", "bn1_var", "bn1_batches", "bn2_mean", "bn2_var", "bn2_batches")]
+
+
 class HowlDecideConfig(ctypes.Structure):
     """``HowlDecideConfig`` of ``include/howl_hip_decide.h``: a host struct; ``weights`` / ``color`` are device pointers."""
     _fields_ = [("mode", c_int), ("C", c_int), ("blank", c_int), ("negative", c_int), ("threshold", c_double), ("smoothing_ms", c_double),
@@ -220,6 +234,15 @@ GRU_SIGNATURES = {
 }
 GRU_SIZE_FUNCS = {"howl_gru_supported": [c_int, c_int, c_int, c_int], "howl_gru_workspace_bytes": [c_int, c_int]}
 
+# The las model's entry points of ``include/howl_hip_las.h`` (``tests/test_emu_las.py`` checks them against that header)
+LAS_SIGNATURES = {
+    "howl_las_fwd": [POINTER(HowlLasParams), POINTER(HowlLasBuffers), P, c_long, c_long, c_long, c_long, c_int, c_int, c_int, c_int, P, c_int,
+                     P, c_float, P, P, c_size_t, STREAM],
+    "howl_las_bwd": [POINTER(HowlLasParams), P, c_long, c_long, c_long, c_long, c_int, c_int, c_int, c_int, P, c_float, P,
+                     POINTER(HowlLasGrads), P, c_size_t, STREAM],
+}
+LAS_SIZE_FUNCS = {"howl_las_supported": [c_int, c_int, c_int, c_int], "howl_las_workspace_bytes": [c_int, c_int]}
+
 
 class HowlHipError(RuntimeError):
     pass
@@ -237,12 +260,12 @@ class Library:
         self.cdll.howl_last_error.restype = c_char_p
         self.cdll.howl_last_error.argtypes = []
         for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES, **LSTM_STREAM_SIGNATURES, **DECIDE_SIGNATURES,
-                               **CTC_LONG_SIGNATURES, **GRU_SIGNATURES}.items():
+                               **CTC_LONG_SIGNATURES, **GRU_SIGNATURES, **LAS_SIGNATURES}.items():
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = c_int
             fn.argtypes = argtypes
         for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS, **LSTM_STREAM_SIZE_FUNCS, **DECIDE_SIZE_FUNCS,
-                               **CTC_LONG_SIZE_FUNCS, **GRU_SIZE_FUNCS}.items():
+                               **CTC_LONG_SIZE_FUNCS, **GRU_SIZE_FUNCS, **LAS_SIZE_FUNCS}.items():
             fn = getattr(self.cdll, name)
             fn.restype = c_size_t
             fn.argtypes = argtypes

@@ -162,7 +162,7 @@ class InferenceEngine:
             if streaming:
                 self.model.streaming_state = state
             return self._run_frames(probs[0].cpu().numpy(), delta_ms)
-        transformed = self.std.log_mel_for_model(audio_data.unsqueeze(0), self.zmuv)
+        transformed = self.std.log_mel_for_model(audio_data.unsqueeze(0), self.zmuv, channels=getattr(self.model, "FEATURE_CHANNELS", 1))
         predictions = self.model(transformed, lengths=None)
         predictions = F.softmax(predictions, -1).squeeze(1).cpu().numpy()   # one device->host copy for all frames
         return self._run_frames(predictions, delta_ms)
@@ -237,7 +237,7 @@ class FrameInferenceEngine(InferenceEngine):
         stride_sz = starts[1] - starts[0] if len(starts) > 1 else chunk
         flat = audio_data.reshape(-1).contiguous()
         windows = flat.as_strided((len(starts), chunk), (stride_sz, 1))   # overlapping views, no copy
-        feats = self.std.log_mel_for_model(windows, self.zmuv)
+        feats = self.std.log_mel_for_model(windows, self.zmuv, channels=getattr(self.model, "FEATURE_CHANNELS", 1))
         lengths = self.std.compute_lengths(torch.full((len(starts),), chunk, device=audio_data.device))
         return self.model(feats, lengths).softmax(-1).cpu().numpy()
 
@@ -279,7 +279,7 @@ class FrameInferenceEngine(InferenceEngine):
                 if not pieces:
                     return
                 windows = pieces[0] if len(pieces) == 1 else torch.cat(pieces)      # (windows of this launch, chunk): the only copy
-                feats = self.std.log_mel_for_model(windows, self.zmuv)
+                feats = self.std.log_mel_for_model(windows, self.zmuv, channels=getattr(self.model, "FEATURE_CHANNELS", 1))
                 lengths = self.std.compute_lengths(torch.full((windows.size(0),), chunk, device=device))
                 parts.append(self.model(feats, lengths).softmax(-1))
                 pieces, held = [], 0
@@ -418,6 +418,6 @@ class FrameInferenceEngine(InferenceEngine):
             return self._append_probability_frame(self._weighted(prediction), curr_time=curr_time)
         lengths = torch.tensor([frame.size(-1)]).to(frame.device)
         transformed_lengths = self.std.compute_lengths(lengths)
-        transformed_frame = self.std.log_mel_for_model(frame.unsqueeze(0), self.zmuv)
+        transformed_frame = self.std.log_mel_for_model(frame.unsqueeze(0), self.zmuv, channels=getattr(self.model, "FEATURE_CHANNELS", 1))
         prediction = self.model(transformed_frame, transformed_lengths).softmax(-1)[0].cpu().numpy()
         return self._append_probability_frame(self._weighted(prediction), curr_time=curr_time)

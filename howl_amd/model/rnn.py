@@ -1,6 +1,8 @@
 """``SequentialLstm`` ("seq-lstm") and ``SimpleLstm`` ("lstm") of ``howl/model/rnn.py:41-91`` on MI355X kernels
 (``howl_amd/csrc/lstm.hip``): packed-sequence LSTM(40 -> 128) + Linear(128,256)-ReLU-Linear(256,C); ``SimpleGru`` ("gru") of
-``howl/model/rnn.py:94-130`` on ``howl_amd/csrc/gru.hip``: conv encoder + GRU(40 -> 96) + Linear-ReLU-Dropout-Linear.
+``howl/model/rnn.py:94-130`` on ``howl_amd/csrc/gru.hip``: conv encoder + GRU(40 -> 96) + Linear-ReLU-Dropout-Linear;
+``LASClassifier`` ("las") of ``howl/model/rnn.py:133-215`` on ``howl_amd/csrc/las.hip``: conv encoder + bidirectional
+LSTM(352 -> 96) + four-head fixed attention + Linear-ReLU-Dropout-Linear.
 
 Same construction order / ``state_dict`` keys (``lstm.weight_ih_l0 ...``, ``dnn.0.*``, ``dnn.2.*``), same call protocol
 ``model(x: (B, C>=1, M, T), lengths)`` and streaming-state protocol as the reference; ``nn.LSTM`` / ``nn.Linear`` are
@@ -18,7 +20,8 @@ from howl_amd.settings import _EnvSettings
 
 from .base import RegisteredModel
 
-__all__ = ["LASEncoderConfig", "LstmConfig", "LstmStreamSession", "SequentialLstm", "SimpleGru", "SimpleLstm"]
+__all__ = ["FixedAttentionModuleConfig", "LASClassifier", "LASClassifierConfig", "LASEncoderConfig", "LstmConfig", "LstmStreamSession",
+           "SequentialLstm", "SimpleGru", "SimpleLstm"]
 
 HID = 128
 
@@ -36,6 +39,23 @@ class LASEncoderConfig(_EnvSettings):
     hidden_size: int = 96
     num_layers: int = 1
     use_maxpool: bool = True
+
+
+class FixedAttentionModuleConfig(_EnvSettings):
+    num_heads: int = 4
+    hidden_size: int = 96
+
+
+class LASClassifierConfig(_EnvSettings):
+    dnn_size: int = 256
+    dropout: float = 0.1
+    las_config: LASEncoderConfig = None              # None: the defaults
+    fixed_attn_config: FixedAttentionModuleConfig = None
+
+    def __init__(self, **overrides):
+        super().__init__(**overrides)
+        self.las_config = self.las_config or LASEncoderConfig()
+        self.fixed_attn_config = self.fixed_attn_config or FixedAttentionModuleConfig()
 
 
 def _vp(t):
@@ -616,3 +636,188 @@ class SimpleGru(RegisteredModel, name="gru"):
 
     def forward(self, x, lengths):
         return _GruFunction.apply(self, x, lengths, None, *self.hot_parameters())
+
+
+class _LasFunction(torch.autograd.Function):
+    """The whole las model as one differentiable function of its twenty-five parameters: ``howl_las_fwd`` / ``howl_las_bwd``."""
+
+    @staticmethod
+    def forward(ctx, model, feat, lengths, t_out, *params):
+        logits = model._launch_forward(feat, lengths, t_out)
+        ctx.model, ctx.feat, ctx.saved = model, feat, model._las_saved
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        ctx.model._las_saved = ctx.saved
+        grads = ctx.model._launch_backward(ctx.feat, dlogits.contiguous())
+        return (None, None, None, None) + tuple(grads)
+
+
+class _LasEncoder(nn.Module):
+    """Parameter container with the reference's names (rnn.py:133-153): conv1 and conv2 are registered twice, as attributes and
+    inside ``conv_encoder``, so both key families appear in the ``state_dict`` and share one tensor each."""
+
+    def __init__(self, config: LASEncoderConfig):
+        super().__init__()
+        c = config.num_latent_channels
+        self.use_maxpool = config.use_maxpool
+        self.conv1 = conv1 = nn.Conv2d(config.num_spec_channels, c, 3, padding=2)
+        self.conv2 = conv2 = nn.Conv2d(c, c, 3, padding=2)
+        self.conv_encoder = nn.Sequential(conv1, nn.BatchNorm2d(c), nn.ReLU(), nn.MaxPool2d((1, 2)), conv2, nn.BatchNorm2d(c), nn.ReLU(),
+                                          nn.MaxPool2d((1, 2)))
+        self.lstm_encoder = nn.LSTM(c * (config.num_mels + 4), config.hidden_size, config.num_layers, bias=True, bidirectional=True)
+
+
+class _FixedAttention(nn.Module):
+    """Parameter container of ``FixedAttentionModule`` (rnn.py:171-177)."""
+
+    def __init__(self, config: FixedAttentionModuleConfig):
+        super().__init__()
+        self.context_vec = nn.Parameter(torch.Tensor(config.hidden_size * 2).uniform_(-0.25, 0.25), requires_grad=True)
+        self.v_proj = nn.Linear(config.hidden_size * 2, config.hidden_size * 2)
+        self.k_proj = nn.Linear(config.hidden_size * 2, config.hidden_size * 2)
+        self.num_heads = config.num_heads
+
+
+class LASClassifier(RegisteredModel, name="las"):
+    """``LASClassifier`` of the reference (rnn.py:133-215) on the kernels of ``howl_amd/csrc/las.hip``, the whole model one C-ABI
+    call per direction: Conv2d(3,8,3,padding=2) - BatchNorm - ReLU - MaxPool(1,2) - Conv2d(8,8,3,padding=2) - BatchNorm - ReLU
+    - MaxPool(1,2) - bidirectional LSTM(352 -> 96) on the packed batch - ``FixedAttentionModule`` (4 heads; the scores come from
+    ``v_proj``, the weighted sum runs over ``k_proj``'s output, as the reference's arithmetic has it) - Linear(192,256) - ReLU
+    - Dropout(0.1) - Linear(256, num_labels).  Same construction order and ``state_dict`` keys, the double registration of conv1 /
+    conv2 included (35 keys, 25 distinct parameters): a reference workspace loads with ``strict=True`` and a saved one loads in the
+    reference; the ``nn`` modules are parameter containers only.
+
+    The whole (B, 3, 40, T) buffer goes through the encoder, padded frames included (they count in the BatchNorm statistics, as
+    in the reference); utterance b's recurrences and attention run ``n_b = (((lengths[b] + 2) // 2) + 2) // 2`` steps.  Decided once:
+
+    * the reference keeps the batch's padded steps ``n_b <= t < max n_b`` in the softmax with an additive -100.  Their ``rnn_seq`` is
+      zero, and their softmax weight is at most e^(-100 + spread) of the largest, which vanishes against 1 in fp32.  The kernels
+      leave these steps out, so an utterance's result never depends on its batch neighbours (the float64 restatement of
+      ``tests/las_util.py`` keeps them: the tests would show if it ever mattered);
+    * this class never writes to ``lengths``;
+    * like ``pack_padded_sequence``, host ``lengths`` must be sorted in decreasing order and lie in 1..T; device-resident lengths
+      together with ``t_out`` are trusted;
+    * any config other than ``num_mels=40, num_spec_channels=3, num_latent_channels=8, hidden_size=96, num_layers=1,
+      use_maxpool=True``, 4 heads and ``dnn_size=256`` raises ``NotImplementedError`` at construction;
+    * dropout draws one ``howl_dropout_mask`` launch per training forward, keyed from torch's CPU generator and salted by the
+      replica rank, unless ``forced_keep_mask`` (B, 256 of 0/1) is set;
+    * the gradients of ``conv1.bias``, ``conv2.bias`` (each in front of a batch-statistics BatchNorm) and ``attn.v_proj.bias`` (a
+      constant under the softmax over time) are identically zero and come back as exact zeros.
+
+    Not sequential; no streaming state."""
+    NEEDS_LENGTHS = True       # FusedTrainer.step passes the frame lengths through
+    FEATURE_CHANNELS = 3       # log-mels, deltas, accelerations: ``log_mel_for_model(channels=3)``
+
+    def __init__(self, num_labels: int, config: LASClassifierConfig = None):
+        super().__init__(num_labels)
+        config = config or LASClassifierConfig()
+        enc, att = config.las_config, config.fixed_attn_config
+        for obj, name, want in ((enc, "num_mels", 40), (enc, "num_spec_channels", 3), (enc, "num_latent_channels", 8), (enc, "hidden_size", 96),
+                                (enc, "num_layers", 1), (enc, "use_maxpool", True), (att, "num_heads", 4), (att, "hidden_size", 96),
+                                (config, "dnn_size", 256)):
+            if getattr(obj, name) != want:
+                raise NotImplementedError(f"the MI355X las kernels are specialised for {name}={want} (got {getattr(obj, name)})")
+        if not 0.0 <= config.dropout < 1.0:
+            raise ValueError(f"dropout must be in [0, 1) (got {config.dropout})")
+        self.encoder = _LasEncoder(enc)
+        self.attn = _FixedAttention(att)
+        self.fc = nn.Sequential(nn.Linear(enc.hidden_size * 2, config.dnn_size), nn.ReLU(), nn.Dropout(config.dropout),
+                                nn.Linear(config.dnn_size, num_labels))
+        self.dropout_p = config.dropout
+        self.forced_keep_mask = None     # tests: (B, 256) 0/1 mask used instead of a fresh draw
+        self._las_saved = None
+
+    def hot_parameters(self):
+        """The 25 distinct parameters in the library's gradient order (``HowlLasGrads``) = ``state_dict`` order without the aliases."""
+        e, r, a, d = self.encoder, self.encoder.lstm_encoder, self.attn, self.fc
+        bn1, bn2 = e.conv_encoder[1], e.conv_encoder[5]
+        return [e.conv1.weight, e.conv1.bias, e.conv2.weight, e.conv2.bias, bn1.weight, bn1.bias, bn2.weight, bn2.bias,
+                r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0, r.weight_ih_l0_reverse, r.weight_hh_l0_reverse,
+                r.bias_ih_l0_reverse, r.bias_hh_l0_reverse, a.context_vec, a.v_proj.weight, a.v_proj.bias, a.k_proj.weight, a.k_proj.bias,
+                d[0].weight, d[0].bias, d[3].weight, d[3].bias]
+
+    def _inputs(self, x, lengths, t_out):
+        """-> (x (B, 3, 40, T), device int64 lengths or None).  Host lengths are checked as ``SimpleGru._inputs`` checks them; device
+        lengths with ``t_out`` (their maximum) are trusted."""
+        if not ops.on_device(x):
+            raise _lib.HowlHipError("las input must be on a HIP device (no CPU fallback)")
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise RuntimeError(f"las reads three feature channels: x must be (B, 3, 40, T), got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise TypeError("las input must be float32")
+        B, T = x.shape[0], x.shape[3]
+        if lengths is not None and t_out is not None and ops.on_device(lengths):
+            if lengths.numel() != B or not 1 <= t_out <= T:
+                raise RuntimeError("lengths must have one entry per sequence and t_out must be in 1..T")
+            lengths = lengths.to(torch.int64)
+        elif lengths is not None:
+            lc = lengths.detach().cpu().long()
+            if lc.numel() != B:
+                raise RuntimeError("lengths must have one entry per sequence")
+            if (lc[:-1] < lc[1:]).any():
+                raise RuntimeError("`lengths` array must be sorted in decreasing order (pack_padded_sequence semantics)")
+            if lc.min() <= 0 or lc.max() > T:
+                raise RuntimeError("lengths must be in 1..T")
+            lengths = lc.to(x.device)
+        return x, lengths
+
+    def _draw_mask(self, B, device):
+        if self.forced_keep_mask is not None:
+            return self.forced_keep_mask.to(device=device, dtype=torch.float32).contiguous()
+        if self.dropout_p <= 0:
+            return None
+        # one launch of the counter-based device generator; the key comes from torch's CPU generator (a host draw: reproducible
+        # under torch.manual_seed, nothing read back from the device)
+        mask = torch.empty((B, 256), dtype=torch.float32, device=device)
+        key = int(torch.randint(0, 2 ** 62, (1,)).item())
+        key ^= (parallel.world_info()[0] * 0x9E3779B97F4A7C15) & (2 ** 62 - 1)   # replicas share the CPU seed, not the mask
+        _lib.get().call("howl_dropout_mask", _vp(mask), mask.numel(), float(self.dropout_p), ctypes.c_ulonglong(key), ops._stream())
+        return mask
+
+    def _bn_buffers(self):
+        bn1, bn2 = self.encoder.conv_encoder[1], self.encoder.conv_encoder[5]
+        return _lib.HowlLasBuffers(_vp(bn1.running_mean), _vp(bn1.running_var), _vp(bn1.num_batches_tracked), _vp(bn2.running_mean),
+                                   _vp(bn2.running_var), _vp(bn2.num_batches_tracked))
+
+    def _launch_forward(self, feat, lengths, t_out=None):
+        """feat (B, 3, 40, T) in any strides, frame lengths (or None = all T) -> logits (B, num_labels); in training mode keeps
+        what ``_launch_backward`` needs (the library's workspace)."""
+        x, lengths = self._inputs(feat, lengths, t_out)
+        B, _, M, T = x.shape
+        cdll = _lib.get().cdll
+        if not cdll.howl_las_supported(B, M, T, self.num_labels):
+            raise _lib.HowlHipError(f"las: B={B}, {M} mel bins, T={T}, {self.num_labels} labels is outside the kernels' range "
+                                    f"(40 mel bins, 1..8192 frames, 1..64 labels)")
+        prm = _lib.HowlLasParams(*[_vp(p) for p in self.hot_parameters()])
+        buf = self._bn_buffers()
+        ws = torch.empty(cdll.howl_las_workspace_bytes(B, T), dtype=torch.uint8, device=x.device)
+        logits = torch.empty((B, self.num_labels), dtype=torch.float32, device=x.device)
+        mask = self._draw_mask(B, x.device) if self.training else None
+        if mask is not None and tuple(mask.shape) != (B, 256):
+            raise RuntimeError(f"forced_keep_mask must be ({B}, 256), got {tuple(mask.shape)}")
+        scale = 1.0 / (1.0 - self.dropout_p) if mask is not None else 1.0
+        _lib.get().call("howl_las_fwd", ctypes.byref(prm), ctypes.byref(buf), _vp(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), B, M,
+                        T, self.num_labels, _vp(lengths), int(self.training), _vp(mask), scale, _vp(logits), _vp(ws), ws.numel(),
+                        ops._stream())
+        self._las_saved = (x, lengths, scale, ws, mask) if self.training else None
+        return logits
+
+    def _launch_backward(self, feat, dlogits, out_grads=None):
+        if self._las_saved is None:
+            raise NotImplementedError("las: the backward pass needs a training-mode forward (eval mode saves nothing)")
+        x, lengths, scale, ws, _ = self._las_saved
+        B, _, M, T = x.shape
+        ps = self.hot_parameters()
+        grads = out_grads if out_grads is not None else [torch.empty_like(p) for p in ps]
+        prm = _lib.HowlLasParams(*[_vp(p) for p in ps])
+        gr = _lib.HowlLasGrads(*[_vp(g) for g in grads])
+        dlogits = dlogits.contiguous()
+        _lib.get().call("howl_las_bwd", ctypes.byref(prm), _vp(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), B, M, T,
+                        self.num_labels, _vp(lengths), scale, _vp(dlogits), ctypes.byref(gr), _vp(ws), ws.numel(), ops._stream())
+        self._las_saved = None
+        return grads
+
+    def forward(self, x, lengths):
+        return _LasFunction.apply(self, x, lengths, None, *self.hot_parameters())

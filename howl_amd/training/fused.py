@@ -1,5 +1,5 @@
 """Fused training step: frontend -> forward -> loss -> backward -> (RCCL all-reduce) -> AdamW.  Frame objective
-(res8, mobilenet, lstm, gru: cross-entropy) and sequence objective (seq-lstm: log_softmax + CTC).
+(res8, mobilenet, lstm, gru, las: cross-entropy) and sequence objective (seq-lstm: log_softmax + CTC).
 
 This is the loop body of ``training/run/pretrain_gsc.py:124-133`` / ``training/run/train.py:286-302`` with every
 stage a C-ABI call on the current HIP stream, gradients written straight into one flat fp32 buffer (the unit of the
@@ -39,8 +39,8 @@ class FlatParams:
 
 class FusedTrainer:
     """Works with any model that exposes ``hot_parameters()`` (flat-buffer order), ``_launch_forward(feat)`` and
-    ``_launch_backward(feat, dlogits, out_grads=views)``: ``Res8``, ``MobileNetClassifier``, ``SimpleLstm`` and ``SimpleGru`` (``step``; the
-    latter two with frame lengths), and with ``SequentialLstm`` (``step_sequence``: ``_launch_forward(feat, lengths)`` /
+    ``_launch_backward(feat, dlogits, out_grads=views)``: ``Res8``, ``MobileNetClassifier``, ``SimpleLstm``, ``SimpleGru`` and ``LASClassifier`` (``step``; the
+    latter three with frame lengths), and with ``SequentialLstm`` (``step_sequence``: ``_launch_forward(feat, lengths)`` /
     ``_launch_backward(dscores, out_grads)``).  With more than one rank the flat gradient is summed over RCCL before the
     fused AdamW (which applies 1/world); res8 overlaps that all-reduce with the tail of its backward pass."""
 
@@ -73,7 +73,7 @@ class FusedTrainer:
         parallel.broadcast_([self.fp.flat] + list(self.model.buffers()), src, self.group)
 
     def features(self, audio):
-        return self.std.log_mel_for_model(audio, self.zmuv)
+        return self.std.log_mel_for_model(audio, self.zmuv, channels=getattr(self.model, "FEATURE_CHANNELS", 1))
 
     def step(self, audio, labels, lengths=None, max_frames=None):
         """One optimisation step on a (B, L) PCM batch; returns the (local) mean loss as a device tensor."""

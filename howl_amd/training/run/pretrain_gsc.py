@@ -122,7 +122,7 @@ def main(argv=None):
                 if k % world != rank:
                     continue
                 batch = bank.batch(torch.tensor(ids))
-                scores = model(std_transform.log_mel_for_model(batch.audio_data, zmuv_transform),
+                scores = model(std_transform.log_mel_for_model(batch.audio_data, zmuv_transform, channels=getattr(model, "FEATURE_CHANNELS", 1)),
                                std_transform.compute_lengths(batch.lengths))
                 counts[0] += (scores.max(1)[1] == batch.labels).float().sum()
                 counts[1] += scores.size(0)
@@ -148,7 +148,7 @@ def main(argv=None):
     workspace.save_settings(SETTINGS)
     writer.add_scalar("Meta/Parameters", sum(p.numel() for p in params))
     if not hasattr(model, "hot_parameters"):
-        raise NotImplementedError(f"{args.model}: no fused MI355X training step (res8, mobilenet, lstm, gru have one)")
+        raise NotImplementedError(f"{args.model}: no fused MI355X training step (res8, mobilenet, lstm, gru, las have one)")
     trainer = FusedTrainer(model, std_transform, zmuv_transform, SETTINGS.training.learning_rate,
                            weight_decay=SETTINGS.training.weight_decay)
     trainer.broadcast_parameters()                                     # rank 0's initial weights and BatchNorm buffers

@@ -207,7 +207,7 @@ def main(argv=None):
     ws.write_args(args)
     ws.save_settings(SETTINGS)
     params = [p for p in model.parameters() if p.requires_grad]
-    fused = (use_frame and args.model in ("res8", "mobilenet", "lstm", "gru")) or (not use_frame and args.model == "seq-lstm")
+    fused = (use_frame and args.model in ("res8", "mobilenet", "lstm", "gru", "las")) or (not use_frame and args.model == "seq-lstm")
     needs_lengths = getattr(model, "NEEDS_LENGTHS", False)
     if fused:
         trainer = FusedTrainer(model, std_transform, zmuv_transform, SETTINGS.training.learning_rate,
@@ -215,7 +215,7 @@ def main(argv=None):
         trainer.broadcast_parameters()                             # rank 0's initial weights and BatchNorm buffers
     elif world > 1:
         raise NotImplementedError(f"{args.model} with the {'frame' if use_frame else 'ctc'} objective has no fused step: "
-                                  "data-parallel training needs one (res8 / mobilenet / lstm / gru: frame, seq-lstm: ctc)")
+                                  "data-parallel training needs one (res8 / mobilenet / lstm / gru / las: frame, seq-lstm: ctc)")
     else:
         optimizer = torch.optim.AdamW(params, SETTINGS.training.learning_rate, weight_decay=SETTINGS.training.weight_decay)
     criterion = torch.nn.CrossEntropyLoss()                        # frame objective; the CTC objective is ops.ctc_loss below
@@ -234,7 +234,7 @@ def main(argv=None):
             if use_frame:
                 batch = collate.frame_batch(examples, batchifier)
                 frame_lengths = std_transform.compute_lengths(batch.lengths)
-                feats = std_transform.log_mel_for_model(batch.audio_data, zmuv_transform)
+                feats = std_transform.log_mel_for_model(batch.audio_data, zmuv_transform, channels=getattr(model, "FEATURE_CHANNELS", 1))
                 for aug in spectrogram_augmentations:              # after ZMUV, for both objectives (train.py:289-290)
                     feats = aug(feats)
                 if fused and needs_lengths:
@@ -250,7 +250,7 @@ def main(argv=None):
             else:
                 batch = collate.sequence_batch(examples, batchifier)
                 frame_lengths = std_transform.compute_lengths(batch.audio_lengths)
-                feats = std_transform.log_mel_for_model(batch.audio_data, zmuv_transform)
+                feats = std_transform.log_mel_for_model(batch.audio_data, zmuv_transform, channels=getattr(model, "FEATURE_CHANNELS", 1))
                 for aug in spectrogram_augmentations:
                     feats = aug(feats)
                 if model.streaming_state is not None and model.streaming_state[0].shape[1] != feats.shape[0]:
