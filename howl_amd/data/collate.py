@@ -17,6 +17,11 @@ here ONE process feeds a ~1 ms device step, so the host side of a batch has to c
 * the per-batch decisions ride to the device in ONE copy out of a ring of pinned staging buffers;
 * ``prefetch(id_batches)`` prepares batch k + 1 (draws, sort, packed buffer) in a worker thread while the caller launches
   batch k and its training step.
+
+``timestretch=True`` puts ``TimestretchTransform`` (``transform.py:146-165``) where ``training/run/train.py:202-221`` has it:
+behind the mixer, in front of Timeshift.  Its draws are the reference's (one gate draw from ``random``, one
+``np.random.normal`` per example); on a batch whose gate opens, ONE ``howl_timestretch_clips`` launch stretches the (mixed)
+clips into a scratch ragged bank and the collate launch reads its windows from there.
 """
 import queue
 import random
@@ -39,12 +44,16 @@ MIXER_DOMAIN, MIXER_IDX, MIXER_PROB = [0.1, 0.2, 0.3, 0.4, 0.5], 1, 0.75
 
 class DeviceCollate:
     def __init__(self, bank_audio, bank_lengths, bank_labels, max_len: int, sr: int = 16000, seed: int = None,
-                 training: bool = True, background=None, do_replace: bool = False, replica: int = 0, row_offsets=None):
+                 training: bool = True, background=None, do_replace: bool = False, replica: int = 0, row_offsets=None,
+                 timestretch: bool = False):
         """``background`` = (bg_audio (N, Lbg) on the device, bg_lengths): the noise dataset of ``DatasetMixer``.
         ``replica``: this process's rank in a data-parallel job -- it keys the device noise generator (and, with a ``seed``, the
         host draws), so that row r of every rank's shard does not receive the same shift / noise pattern.
         ``row_offsets``: ragged bank -- ``bank_audio`` is the (total, 1) view of a flat sample buffer and clip i starts at
-        sample ``row_offsets[i]`` (``WakeWordClipBank``); default: a dense (N, Lmax) matrix, clip i = row i."""
+        sample ``row_offsets[i]`` (``WakeWordClipBank``); default: a dense (N, Lmax) matrix, clip i = row i.
+        ``timestretch``: ``frame_batch`` / ``sequence_batch`` apply ``TimestretchTransform`` (default off: every draw stream is the
+        one it was).  Its normal draws come from the global ``np.random`` without a ``seed`` (the reference's generator, seeded by
+        ``set_random_seed``), else from a private ``RandomState`` keyed by seed and replica."""
         self.audio, self.lengths, self.labels = bank_audio, [int(v) for v in bank_lengths.tolist()], bank_labels
         self.last_max_len = 0      # longest row of the last batch (host knowledge: no read-back for the frame count)
         self.labels_host = None if bank_labels is None else [int(v) for v in bank_labels.tolist()]   # gathered on the host
@@ -63,6 +72,11 @@ class DeviceCollate:
         self._rows_np = None if self.row_offsets is None else np.asarray(self.row_offsets, dtype=np.int64)
         self._np_rs = np.random.RandomState(0)
         self._ring, self._ring_next = [], 0
+        self.timestretch, self.last_rates = timestretch, None
+        if timestretch:
+            from howl_amd.data.transform.transform import TimestretchTransform
+            np_rand = None if seed is None else np.random.RandomState([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, replica, 0x54535452])
+            self._stretch = TimestretchTransform(np_rand=np_rand).train(training)
 
     @property
     def rand(self):
@@ -82,6 +96,11 @@ class DeviceCollate:
         n = len(clip_ids)
         lens = [min(self.lengths[i], self.max_len) for i in clip_ids]            # truncate_length
         self.last_mix = self.draw_mixer(lens)                                     # DatasetMixer comes first (train.py:218)
+        self.last_rates, self.last_in_lens = None, lens
+        if self.timestretch:                                                      # then TimestretchTransform (train.py:203)
+            self.last_rates = self._stretch.draw_rates(lens, rand=self.rand)
+            if self.last_rates is not None:                                       # Timeshift's bound sees the stretched length
+                lens = np.rint(np.asarray(lens) / np.asarray(self.last_rates)).astype(np.int64).tolist()     # round(len / rate), half to even
         shift, head = [0] * n, [0] * n
         if self.rand.random() < TIMESHIFT_PROB and self.training:                 # AugmentModule.forward gate
             for k in range(n):
@@ -206,16 +225,32 @@ class DeviceCollate:
             out.append(v if kind == "i" else v.view(torch.float32 if kind == "f" else torch.int64).reshape(shape))
         return out
 
+    def _stretch_clips(self, clip_ids):
+        """The batch's clips through ``TimestretchTransform`` at ``self.last_rates`` (mixed with their backgrounds while they
+        are read, as the reference mixes before it stretches): one upload, one ``howl_timestretch_clips`` launch.  Returns
+        (the scratch ragged bank as a (total, 1) view, the sample offset of every clip in it)."""
+        rows = clip_ids if self.row_offsets is None else [self.row_offsets[i] for i in clip_ids]
+        has_mix = self.last_mix is not None and any(a != 0.0 for a in self.last_mix[2])
+        rec, total = ops.stretch_records(rows, self.last_in_lens, self.last_rates, self.last_mix if has_mix else None)
+        (rec_dev,) = self._upload([("l", rec.view(np.int64))])
+        flat = ops.time_stretch(self.audio, rec, rec_dev, total, bg=self.bg_audio if has_mix else None)
+        return flat.reshape(-1, 1), [int(v) for v in rec["dst_off"]]
+
     def _launch(self, clip_ids, rows, shift, src_end, sigma, sp, lout, dst_off=None, extra=()):
         """One ``howl_collate_augment_window`` launch: batch row r takes samples [shift[r], src_end[r]) of clip
         ``clip_ids[rows[r]]`` (mixed with its background first, noise added), at column ``dst_off[r]``.  ``extra``: more
-        (kind, values) sections to ride in the same upload (labels, lengths); returns (audio, [extra tensors])."""
+        (kind, values) sections to ride in the same upload (labels, lengths); returns (audio, [extra tensors]).
+        On a batch with time stretch the clips are stretched (and mixed) first and the launch reads the scratch bank."""
         pick = lambda a: [a[k] for k in rows]
+        bank = self.audio
+        if self.last_rates is not None:
+            bank, bank_rows = self._stretch_clips(clip_ids)
+        else:
+            bank_rows = clip_ids if self.row_offsets is None else [self.row_offsets[i] for i in clip_ids]
         self._calls += 1
-        bank_rows = clip_ids if self.row_offsets is None else [self.row_offsets[i] for i in clip_ids]
         sections = [("i", pick(bank_rows)), ("i", src_end), ("i", shift), ("i", [1] * len(rows)), ("f", pick(sigma)),
                     ("f", pick(sp))]
-        has_mix = self.last_mix is not None and any(a != 0.0 for a in self.last_mix[2])
+        has_mix = self.last_rates is None and self.last_mix is not None and any(a != 0.0 for a in self.last_mix[2])
         if has_mix:
             sections += [("i", pick(self.last_mix[0])), ("i", pick(self.last_mix[1])), ("f", pick(self.last_mix[2]))]
         if dst_off is not None:
@@ -224,7 +259,7 @@ class DeviceCollate:
         dev_t = self._upload(sections + list(extra))
         idx, end, sh, ones, sg, spp = dev_t[:6]
         mix = (self.bg_audio, dev_t[6], dev_t[7], dev_t[8]) if has_mix else None
-        audio = ops.collate_augment(self.audio, idx, end, sh, ones, sg, spp, ((self._seed << 32) ^ self._calls ^ self._replica_key) & 0xFFFFFFFFFFFFFFFF, lout, mix=mix,
+        audio = ops.collate_augment(bank, idx, end, sh, ones, sg, spp, ((self._seed << 32) ^ self._calls ^ self._replica_key) & 0xFFFFFFFFFFFFFFFF, lout, mix=mix,
                                     dst_off=dev_t[n_own - 1] if dst_off is not None else None)
         return audio, dev_t[n_own:]
 
@@ -232,6 +267,9 @@ class DeviceCollate:
         """Host half of ``__call__``: the draws of the batch (reference order), the length sort and the packed staging buffer.
         No device work, so a worker thread may run it for batch k + 1 while batch k trains (``prefetch``); batches must be
         prepared in the order they are consumed (the draws are one stream)."""
+        if self.timestretch:
+            raise NotImplementedError("DeviceCollate(timestretch=True): whole-clip classification batches (pretrain_gsc) take no time "
+                                      "stretch in the reference either; use frame_batch / sequence_batch")
         # DatasetMixer's rejection loops stay scalar draws; so does a generator that is not a Mersenne Twister with an
         # exportable state (a test double assigned to ``self.rand``)
         if self.bg_audio is not None or not (self._rand is random or isinstance(self._rand, random.Random)):
@@ -334,14 +372,16 @@ class DeviceCollate:
         return ClassificationBatch(audio, ex[1] if self.labels_host is not None else None, ex[0])
 
     def frame_batch(self, examples, batchifier) -> ClassificationBatch:
-        """compose([DatasetMixer,] Timeshift, Noise, WakeWordFrameBatchifier) (train.py:211-229) on device clips: the
+        """compose([DatasetMixer,] [Timestretch,] Timeshift, Noise, WakeWordFrameBatchifier) (train.py:202-229) on device clips: the
         augmentation draws come first (per batch, reference order), the batchifier then picks one window per augmented
         clip -- word end times are NOT corrected for a head crop, as in the reference -- and one launch produces the batch."""
         from howl_amd.data.transform.batchifier import DeviceClip
         clip_ids = [ex.clip_id for ex in examples]
         lens, shift, head, sigma, sp = self.draw(clip_ids)
-        cropped = [DeviceClip(ex.clip_id, l - w, ex.timestamp_label_map, ex.transcription)
-                   for ex, l, w in zip(examples, lens, shift)]
+        maps = [ex.timestamp_label_map for ex in examples]
+        if self.last_rates is not None:                                          # update_audio_data(scale=1 / rate), example.py:97-98
+            maps = [self._stretch.scale_labels(m, r) for m, r in zip(maps, self.last_rates)]
+        cropped = [DeviceClip(ex.clip_id, l - w, m, ex.transcription) for ex, l, w, m in zip(examples, lens, shift, maps)]
         plan = batchifier.plan(cropped)
         first = [(shift[k] if head[k] else 0) + a for k, a in zip(plan.source, plan.start)]
         audio, ex = self._launch(clip_ids, plan.source, first, [f + n for f, n in zip(first, plan.length)], sigma, sp,
@@ -349,7 +389,7 @@ class DeviceCollate:
         return ClassificationBatch(audio, ex[0], torch.tensor(plan.length))
 
     def sequence_batch(self, examples, batchifier):
-        """compose([DatasetMixer,] Timeshift, Noise, AudioSequenceBatchifier) (train.py:206-229): whole augmented clips,
+        """compose([DatasetMixer,] [Timestretch,] Timeshift, Noise, AudioSequenceBatchifier) (train.py:202-229): whole augmented clips,
         ``np.argsort(-lengths)`` order, zero padded on the right; labels from the batchifier's tokenizer."""
         from howl_amd.data.common.batch import SequenceBatch
         clip_ids = [ex.clip_id for ex in examples]

@@ -18,7 +18,7 @@ from howl_amd import ops
 from howl_amd.lib import MAX_MELS, fb_packed_floats
 from howl_amd.settings import SETTINGS
 
-__all__ = ["AugmentationParameter", "AugmentModule", "StandardAudioTransform", "SpecAugmentTransform",
+__all__ = ["AugmentationParameter", "AugmentModule", "StandardAudioTransform", "SpecAugmentTransform", "TimestretchTransform",
            "mel_corner_points", "vtlp_warp_points"]
 
 
@@ -211,6 +211,54 @@ class StandardAudioTransform(AugmentModule):
             self.rand.random()  # forward()'s draw happens on every call, eval mode included (transform.py:93): keep the stream's position
         rec, feat, keep = ops.logmel_args(audio, self._standard_fb(), self.n_mels, zmuv.pair() if zmuv is not None else None, layout=1)
         return rec, feat.permute(0, 2, 1).unsqueeze(1), keep
+
+
+class TimestretchTransform(AugmentModule):
+    """``transform.py:146-165``: per batch one gate draw from ``rand`` (prob 0.8), then per example a rate from
+    ``np.random.normal(1.0, magnitude)`` clipped to [0.3, 1.7]; the clip becomes ``round(len / rate)`` samples and its word end
+    times are multiplied by ``1 / rate`` (``example.py:97-98``).  This module holds the host decisions; the samples are made by
+    ``ops.time_stretch`` (one ``howl_timestretch_clips`` launch for the batch), which ``DeviceCollate(timestretch=True)`` issues.
+
+    ``np_rand``: where the normal draws come from -- the global ``np.random`` (the reference's; ``set_random_seed`` seeds it) or a
+    ``np.random.RandomState`` of the caller's.  A clip under ``MIN_SAMPLES`` (one transform frame) keeps rate 1.0 and still
+    consumes its draw."""
+    MIN_SAMPLES = 2048
+    MIN_RATE, MAX_RATE = 0.3, 1.7
+    N_FFT, HOP = 2048, 512
+
+    def __init__(self, seed: int = None, np_rand=None):
+        super().__init__(seed)
+        self.np_rand = np.random if np_rand is None else np_rand
+
+    @property
+    def default_params(self) -> Sequence[AugmentationParameter]:
+        return (AugmentationParameter([0.1, 0.2, 0.3], "timestretch", 1, prob=0.8),)
+
+    def draw_rates(self, lengths: Sequence[int], rand=None):
+        """The draws of one batch in the reference's order: None when the gate is closed, else one rate per example."""
+        param = self.augment_params[0]
+        rand = self.rand if rand is None else rand
+        if not (param.enabled and rand.random() < param.prob and self.training):
+            return None
+        # one array draw: RandomState.normal(size=n) is n successive scalar draws, value for value
+        rates = np.clip(self.np_rand.normal(1.0, param.magnitude, len(lengths)), self.MIN_RATE, self.MAX_RATE)
+        rates[np.asarray(lengths) < self.MIN_SAMPLES] = 1.0
+        return rates.tolist()
+
+    @classmethod
+    def stretched_length(cls, length: int, rate: float) -> int:
+        """``librosa.effects.time_stretch``: ``int(round(len / rate))`` (Python's round: half to even)."""
+        return int(round(length / rate))
+
+    @classmethod
+    def num_steps(cls, length: int, rate: float) -> int:
+        """``len(np.arange(0, n_in, rate))`` for the ``n_in = 1 + len // 512`` frames of the clip's spectrogram."""
+        return int(math.ceil((1 + length // cls.HOP) / rate))
+
+    @staticmethod
+    def scale_labels(timestamp_label_map, rate: float):
+        scale = 1 / rate
+        return {scale * k: v for k, v in timestamp_label_map.items()}
 
 
 class SpecAugmentTransform(AugmentModule):

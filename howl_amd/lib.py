@@ -243,6 +243,18 @@ LAS_SIGNATURES = {
 }
 LAS_SIZE_FUNCS = {"howl_las_supported": [c_int, c_int, c_int, c_int], "howl_las_workspace_bytes": [c_int, c_int]}
 
+# The time-stretch entry point of ``include/howl_hip_timestretch.h`` (``tests/test_emu_timestretch.py`` checks the table against that
+# header).  ``clips_host`` is a HOST pointer to ``HowlStretchClip`` records (``STRETCH_CLIP_DTYPE``), ``clips_dev`` their device copy.
+TIMESTRETCH_SIGNATURES = {
+    "howl_timestretch_clips": [P, c_long, c_long, P, c_long, c_long, c_void_p, P, c_int, P, c_long, ctypes.c_uint, STREAM],
+}
+TIMESTRETCH_SIZE_FUNCS = {}
+TIMESTRETCH_NO_COPY = 1                                                             # HOWL_TIMESTRETCH_NO_COPY
+TIMESTRETCH_MIN_SAMPLES = 2048                                                      # HOWL_TIMESTRETCH_MIN_SAMPLES
+# ``HowlStretchClip`` as a numpy record (48 bytes, no padding)
+STRETCH_CLIP_FIELDS = [("rate", "<f8"), ("src_row", "<i8"), ("dst_off", "<i8"), ("len", "<i4"), ("out_len", "<i4"), ("n_out", "<i4"),
+                       ("bg_idx", "<i4"), ("bg_off", "<i4"), ("alpha", "<f4")]
+
 
 class HowlHipError(RuntimeError):
     pass
@@ -260,12 +272,12 @@ class Library:
         self.cdll.howl_last_error.restype = c_char_p
         self.cdll.howl_last_error.argtypes = []
         for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES, **LSTM_STREAM_SIGNATURES, **DECIDE_SIGNATURES,
-                               **CTC_LONG_SIGNATURES, **GRU_SIGNATURES, **LAS_SIGNATURES}.items():
+                               **CTC_LONG_SIGNATURES, **GRU_SIGNATURES, **LAS_SIGNATURES, **TIMESTRETCH_SIGNATURES}.items():
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = c_int
             fn.argtypes = argtypes
         for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS, **LSTM_STREAM_SIZE_FUNCS, **DECIDE_SIZE_FUNCS,
-                               **CTC_LONG_SIZE_FUNCS, **GRU_SIZE_FUNCS, **LAS_SIZE_FUNCS}.items():
+                               **CTC_LONG_SIZE_FUNCS, **GRU_SIZE_FUNCS, **LAS_SIZE_FUNCS, **TIMESTRETCH_SIZE_FUNCS}.items():
             fn = getattr(self.cdll, name)
             fn.restype = c_size_t
             fn.argtypes = argtypes

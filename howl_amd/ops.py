@@ -140,6 +140,43 @@ def collate_augment(bank, idx, src_len, shift, from_head, sigma, sp_prob, seed, 
     return out
 
 
+def stretch_records(src_rows, lengths, rates, mix=None):
+    """``HowlStretchClip`` records (a numpy record array, ``lib.STRETCH_CLIP_FIELDS``) for clips of ``lengths`` samples at bank
+    rows ``src_rows`` stretched by ``rates``, their outputs back to back; returns (records, total output samples).
+    ``mix`` = (bg_idx, bg_off, alpha) per clip (``DatasetMixer``'s draws)."""
+    n = len(lengths)
+    rec = np.zeros(n, dtype=np.dtype(_lib.STRETCH_CLIP_FIELDS))
+    lens = np.asarray(lengths, dtype=np.int64)
+    rec["rate"], rec["src_row"], rec["len"] = rates, src_rows, lens
+    rec["out_len"] = np.rint(lens / rec["rate"])                                                # Python's round (half to even), as librosa
+    rec["n_out"] = np.ceil((1 + lens // 512) / rec["rate"])                                     # len(np.arange(0, n_in, rate))
+    rec["dst_off"] = np.cumsum(rec["out_len"], dtype=np.int64) - rec["out_len"]
+    if mix is not None:
+        rec["bg_idx"], rec["bg_off"], rec["alpha"] = mix
+    return rec, int(rec["out_len"].sum(dtype=np.int64))
+
+
+def time_stretch(bank, records, records_dev, total, bg=None, through_transform=False):
+    """``TimestretchTransform`` for a batch of ragged clips in one launch: ``records`` (``stretch_records``) are read on the
+    host, ``records_dev`` (the same bytes in device memory, e.g. an int64 tensor) by the kernel; returns the flat (``total``,)
+    buffer of stretched clips, clip b at ``records["dst_off"][b]`` -- viewed (total, 1) it is a ragged bank for
+    ``collate_augment``.  ``bank``: (N, Lmax), or the (total, 1) view of a flat buffer with ``src_row`` = sample offset.
+    ``bg``: the background bank of the records' mix.  A clip of rate 1.0 is copied unless ``through_transform``."""
+    records = np.ascontiguousarray(records)
+    if records.dtype.itemsize != 48:
+        raise TypeError("records must be HowlStretchClip records (ops.stretch_records)")
+    if not on_device(records_dev):
+        _p(records_dev)
+    if records_dev.numel() * records_dev.element_size() < records.nbytes or records_dev.data_ptr() % 8:
+        raise ValueError("records_dev must hold the records' bytes at an 8-byte aligned address")
+    out = torch.empty(max(total, 1), dtype=torch.float32, device=bank.device)
+    _lib.get().call("howl_timestretch_clips", _p(bank), bank.stride(0), bank.numel(), _p(bg, allow_none=True),
+                    0 if bg is None else bg.stride(0), 0 if bg is None else bg.numel(), ctypes.c_void_p(records.ctypes.data),
+                    ctypes.c_void_p(records_dev.data_ptr()), len(records), _p(out), total,
+                    _lib.TIMESTRETCH_NO_COPY if through_transform else 0, _stream())
+    return out[:total]
+
+
 def gather_windows(bank, idx, start, length, dst_off, lout):
     """Rows ``bank[idx[b], start[b]:start[b]+length[b]]`` placed at column ``dst_off[b]`` of a zero (B, lout) batch."""
     B = idx.numel()

@@ -10,7 +10,9 @@ What is different is where the work happens.  The reference decodes and collates
 split is decoded once into a device-resident clip bank (``WakeWordClipBank``) and the collate chain of ``train.py:211-229``
 -- ``[DatasetMixer,] TimeshiftTransform, NoiseTransform, WakeWordFrameBatchifier | AudioSequenceBatchifier`` -- is a set of
 host decisions (the reference's draws, in its order) followed by ONE device launch per batch (``DeviceCollate``).
-``TimestretchTransform`` (librosa phase vocoder) is outside the hot path and not applied.
+``TimestretchTransform``, the first stage of that chain (``train.py:203``; librosa's phase vocoder on the CPU, per clip), is
+applied with ``--timestretch`` (or ``HOWL_TIMESTRETCH=1``): the reference's draws, one ``howl_timestretch_clips`` launch per
+batch in front of the collate launch, word end times rescaled.  Off by default, like the project's other switches.
 
 Datasets: ``-i`` takes Howl-format dataset directories (``aligned-metadata-{training,dev,test}.jsonl`` + ``audio/*.wav``,
 16 kHz mono int16 -- resampling / other codecs are the reference's librosa path and out of scope); ``--synthetic N``
@@ -20,6 +22,7 @@ sequence, negatives shuffled / partial sequences) in the same metadata form, so 
 import argparse
 import csv
 import logging
+import os
 import random
 from pathlib import Path
 from types import SimpleNamespace
@@ -92,6 +95,8 @@ def main(argv=None):
     ap.add_argument("--eval-freq", type=int, default=10)
     ap.add_argument("--eval", action="store_true")
     ap.add_argument("--synthetic", type=int, default=0, help="number of generated positive training clips (no -i needed)")
+    ap.add_argument("--timestretch", action="store_true", default=os.environ.get("HOWL_TIMESTRETCH") == "1",
+                    help="apply TimestretchTransform in the training collate (train.py:203 of the reference); also HOWL_TIMESTRETCH=1")
     args = ap.parse_args(argv)
     if not args.synthetic and not args.dataset_paths:
         raise SystemExit("training.run.train: give Howl-format dataset directories with -i, or --synthetic N")
@@ -144,7 +149,8 @@ def main(argv=None):
     else:
         batchifier = AudioSequenceBatchifier(ctx.negative_label, WakeWordTokenizer(ctx.vocab, ignore_oov=False))
     collate = DeviceCollate(train_bank.rows, train_bank.lengths, None, max_len=train_bank.max_len, row_offsets=train_bank.offsets,
-                            seed=(SETTINGS.training.seed ^ 0x5DEECE66D) if world > 1 else None, replica=rank)
+                            seed=(SETTINGS.training.seed ^ 0x5DEECE66D) if world > 1 else None, replica=rank,
+                            timestretch=args.timestretch)
 
     std_transform = StandardAudioTransform().to(device).eval()
     zmuv_transform = ZmuvTransform().to(device)
