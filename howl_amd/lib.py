@@ -117,6 +117,19 @@ class HowlLasBuffers(ctypes.Structure):
     _fields_ = [(n, P) for n in ("bn1_mean", "bn1_var", "bn1_batches", "bn2_mean", "bn2_var", "bn2_batches")]
 
 
+class HowlCnnParams(ctypes.Structure):
+    """``HowlCnnParams`` / ``HowlCnnGrads`` of ``include/howl_hip_cnn.h``: the twelve tensors in ``state_dict`` order."""
+    _fields_ = [(n, P) for n in ("conv0_w", "conv0_b", "bn1_w", "bn1_b", "conv1_w", "conv1_b", "bn2_w", "bn2_b", "w1", "b1", "w2", "b2")]
+
+
+class HowlCnnGrads(ctypes.Structure):
+    _fields_ = list(HowlCnnParams._fields_)
+
+
+class HowlCnnBuffers(ctypes.Structure):
+    _fields_ = [(n, P) for n in ("bn1_mean", "bn1_var", "bn1_batches", "bn2_mean", "bn2_var", "bn2_batches")]
+
+
 class HowlDecideConfig(ctypes.Structure):
     """``HowlDecideConfig`` of ``include/howl_hip_decide.h``: a host struct; ``weights`` / ``color`` are device pointers."""
     _fields_ = [("mode", c_int), ("C", c_int), ("blank", c_int), ("negative", c_int), ("threshold", c_double), ("smoothing_ms", c_double),
@@ -243,6 +256,17 @@ LAS_SIGNATURES = {
 }
 LAS_SIZE_FUNCS = {"howl_las_supported": [c_int, c_int, c_int, c_int], "howl_las_workspace_bytes": [c_int, c_int]}
 
+# The small-cnn / seq-cnn entry points of ``include/howl_hip_cnn.h`` (``tests/test_emu_cnn.py`` checks them against that header)
+CNN_SMALL, CNN_SEQ = 0, 1                                                           # HOWL_CNN_SMALL, HOWL_CNN_SEQ
+CNN_SIGNATURES = {
+    "howl_cnn_fwd": [c_int, POINTER(HowlCnnParams), POINTER(HowlCnnBuffers), P, c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_int, P,
+                     c_float, P, P, c_size_t, STREAM],
+    "howl_cnn_bwd": [c_int, POINTER(HowlCnnParams), P, c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_float, P, POINTER(HowlCnnGrads),
+                     P, c_size_t, STREAM],
+}
+CNN_SIZE_FUNCS = {"howl_cnn_supported": [c_int, c_int, c_int, c_int, c_int], "howl_cnn_workspace_bytes": [c_int, c_int, c_int, c_int],
+                  "howl_cnn_out_rows": [c_int, c_int]}
+
 # The time-stretch entry point of ``include/howl_hip_timestretch.h`` (``tests/test_emu_timestretch.py`` checks the table against that
 # header).  ``clips_host`` is a HOST pointer to ``HowlStretchClip`` records (``STRETCH_CLIP_DTYPE``), ``clips_dev`` their device copy.
 TIMESTRETCH_SIGNATURES = {
@@ -272,12 +296,13 @@ class Library:
         self.cdll.howl_last_error.restype = c_char_p
         self.cdll.howl_last_error.argtypes = []
         for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES, **LSTM_STREAM_SIGNATURES, **DECIDE_SIGNATURES,
-                               **CTC_LONG_SIGNATURES, **GRU_SIGNATURES, **LAS_SIGNATURES, **TIMESTRETCH_SIGNATURES}.items():
+                               **CTC_LONG_SIGNATURES, **GRU_SIGNATURES, **LAS_SIGNATURES, **TIMESTRETCH_SIGNATURES, **CNN_SIGNATURES}.items():
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = c_int
             fn.argtypes = argtypes
         for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS, **LSTM_STREAM_SIZE_FUNCS, **DECIDE_SIZE_FUNCS,
-                               **CTC_LONG_SIZE_FUNCS, **GRU_SIZE_FUNCS, **LAS_SIZE_FUNCS, **TIMESTRETCH_SIZE_FUNCS}.items():
+                               **CTC_LONG_SIZE_FUNCS, **GRU_SIZE_FUNCS, **LAS_SIZE_FUNCS, **TIMESTRETCH_SIZE_FUNCS,
+                               **CNN_SIZE_FUNCS}.items():
             fn = getattr(self.cdll, name)
             fn.restype = c_size_t
             fn.argtypes = argtypes

@@ -3,7 +3,8 @@
 The module keeps the reference's construction order (so ``set_random_seed`` gives the same initial weights), its
 ``state_dict`` keys / shapes (``conv0.weight``, ``bn{i}.running_mean|running_var|num_batches_tracked``,
 ``conv{i}.weight``, ``output.weight|bias``) and its call protocol ``model(x: (B, C>=1, M, T), lengths)``; the
-submodules are parameter containers only -- forward and backward are single C-ABI calls.
+submodules are parameter containers only -- forward and backward are single C-ABI calls.  ``MobileNetClassifier``
+(``howl_amd/csrc/mobilenet.hip``) and ``SmallCnn`` / ``SequentialCnn`` (``howl_amd/csrc/cnn.hip``) follow the same pattern.
 """
 import ctypes
 import logging
@@ -18,7 +19,7 @@ from howl_amd.settings import _EnvSettings
 
 from .base import RegisteredModel
 
-__all__ = ["Res8", "Res8Settings", "Res8StreamSession", "MobileNetClassifier"]
+__all__ = ["Res8", "Res8Settings", "Res8StreamSession", "MobileNetClassifier", "CnnSettings", "SmallCnn", "SequentialCnn"]
 
 
 class Res8Settings(_EnvSettings):
@@ -623,3 +624,249 @@ class MobileNetClassifier(RegisteredModel, name="mobilenet"):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.hot_parameters()):
             return _MobileNetFunction.apply(self, x, *self.hot_parameters())
         return self._launch_forward(x)
+
+
+# ---- small-cnn / seq-cnn (howl/model/cnn.py:32-104) on howl_amd/csrc/cnn.hip ---------------------------------------------------------
+
+class CnnSettings(_EnvSettings):
+    num_labels: int = 2
+    num_maps1: int = 48
+    num_maps2: int = 64
+    num_hidden_input: int = 384
+    hidden_size: int = 128
+
+
+def cnn_labels_message(model):
+    """The reference sizes the head of ``SmallCnn`` / ``SequentialCnn`` from ``CnnSettings.num_labels`` (env ``NUM_LABELS``, default
+    2), not from the constructor argument; this says so when the two differ (None when they agree or for other models)."""
+    if not isinstance(model, _CnnBase) or model.config.num_labels == model.requested_num_labels:
+        return None
+    return (f"{model.NAME}: the head has CnnSettings.num_labels={model.config.num_labels} outputs (env NUM_LABELS, default 2), as in the "
+            f"reference, not the {model.requested_num_labels} labels the model was constructed for: export NUM_LABELS="
+            f"{model.requested_num_labels}")
+
+
+def require_supported_labels(model):
+    """For the entry points (training.run.*), which know the label space: fail before the first batch."""
+    msg = cnn_labels_message(model)
+    if msg:
+        raise ValueError(msg)
+
+
+class _CnnFunction(torch.autograd.Function):
+    """Either model as one differentiable function of its twelve parameters: ``howl_cnn_fwd`` / ``howl_cnn_bwd``."""
+
+    @staticmethod
+    def forward(ctx, model, feat, *params):
+        out = model._launch_forward(feat)
+        ctx.model, ctx.feat, ctx.version = model, feat, model._fwd_version
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        model = ctx.model
+        if ctx.version != model._fwd_version:
+            raise RuntimeError(f"{model.NAME}: backward called after a newer forward overwrote the saved activations")
+        grads = _CnnBase._launch_backward(model, ctx.feat, dout)
+        return (None, None) + tuple(grads)
+
+
+class _CnnBase(RegisteredModel):
+    """The two-stage conv encoder both models share (``howl_amd/csrc/cnn.hip``): the whole model is one C-ABI call per direction,
+    the ``nn`` submodules are parameter containers in the reference's construction order and with its ``state_dict`` keys
+    (``encoder1.{0,3}.*``, ``encoder2.{0,3}.*``, ``output.{0,3}.*``), so a reference workspace loads with ``strict=True``.
+
+    Kept from the reference on purpose: the head's width is ``config.num_labels`` (``NUM_LABELS``), not the constructor argument
+    (a warning at construction when they differ; the entry points raise); padded frames go through the encoder and count in
+    the BatchNorm statistics, ``lengths`` is ignored.  Only ``num_maps1=48, num_maps2=64, hidden_size=128`` and 40 mel bins are
+    built.  Dropout draws one ``howl_dropout_mask`` launch per training forward, keyed from torch's CPU generator and salted by
+    the replica rank, unless ``forced_keep_mask`` is set."""
+    KIND = None
+    NAME = None
+    CONV0 = None
+
+    def __init__(self, num_labels: int, config: CnnSettings = None):
+        super().__init__(num_labels)
+        config = config or CnnSettings()
+        self.config = config
+        self.requested_num_labels = num_labels
+        for name, want in (("num_maps1", 48), ("num_maps2", 64), ("hidden_size", 128), ("num_hidden_input", 384)):
+            if getattr(config, name) != want:
+                raise NotImplementedError(f"the MI355X {self.NAME} kernels are specialised for {name}={want} (got {getattr(config, name)})")
+        self.num_labels = config.num_labels           # what the scores have: the reference's quirk
+        msg = cnn_labels_message(self)
+        if msg:
+            logging.getLogger(__name__).warning(msg)
+        kernel, pad, stride = self.CONV0
+        conv0 = nn.Conv2d(1, config.num_maps1, kernel, padding=pad, stride=stride, bias=True)
+        pool = nn.MaxPool2d(2)
+        conv1 = nn.Conv2d(config.num_maps1, config.num_maps2, (5, 5), padding=2, stride=(2, 1), bias=True)
+        self.encoder1 = nn.Sequential(conv0, nn.ReLU(), pool, nn.BatchNorm2d(config.num_maps1, affine=True))
+        self.encoder2 = nn.Sequential(conv1, nn.ReLU(), pool, nn.BatchNorm2d(config.num_maps2, affine=True))
+        self.output = nn.Sequential(nn.Linear(self._head_inputs(config), config.hidden_size), nn.ReLU(), nn.Dropout(0.1),
+                                    nn.Linear(config.hidden_size, config.num_labels))
+        self.dropout_p = 0.1
+        self.forced_keep_mask = None     # tests: a 0/1 mask of _mask_shape() used instead of a fresh draw
+        self._cnn_saved = None
+        self._fwd_version = 0
+
+    def hot_parameters(self):
+        """Parameters in the library's gradient order (``HowlCnnGrads``) = ``state_dict`` order."""
+        a, b, o = self.encoder1, self.encoder2, self.output
+        return [a[0].weight, a[0].bias, a[3].weight, a[3].bias, b[0].weight, b[0].bias, b[3].weight, b[3].bias, o[0].weight, o[0].bias,
+                o[3].weight, o[3].bias]
+
+    @classmethod
+    def out_rows(cls, T: int) -> int:
+        """Rows of the encoder's output for T frames (0 outside the kernels' range): ``howl_cnn_out_rows``."""
+        return int(_lib.get().cdll.howl_cnn_out_rows(cls.KIND, int(T)))
+
+    def _draw_mask(self, shape, device):
+        if self.forced_keep_mask is not None:
+            mask = self.forced_keep_mask.to(device=device, dtype=torch.float32).contiguous()
+            if tuple(mask.shape) != tuple(shape):
+                raise RuntimeError(f"forced_keep_mask must be {tuple(shape)}, got {tuple(mask.shape)}")
+            return mask
+        if self.dropout_p <= 0:
+            return None
+        mask = torch.empty(shape, dtype=torch.float32, device=device)
+        key = int(torch.randint(0, 2 ** 62, (1,)).item())
+        key ^= (parallel.world_info()[0] * 0x9E3779B97F4A7C15) & (2 ** 62 - 1)   # replicas share the CPU seed, not the mask
+        _lib.get().call("howl_dropout_mask", _vp(mask), mask.numel(), float(self.dropout_p), ctypes.c_ulonglong(key), ops._stream())
+        return mask
+
+    def _launch_forward(self, feat, lengths=None, t_out=None):
+        """feat (B, C>=1, 40, T) -> the scores; in training mode keeps what ``_launch_backward`` needs (the library's workspace).
+        ``lengths`` / ``t_out`` are accepted for the trainers' call protocol and ignored, as the reference ignores them."""
+        if feat.dim() != 4:
+            raise ValueError(f"{self.NAME}: features must be (B, C, 40, T), got {tuple(feat.shape)}")
+        x0 = feat[:, 0]
+        B, M, T = x0.shape
+        if M != 40:
+            raise ValueError(f"{self.NAME} on MI355X is built for NUM_MELS=40, got {M} mel bins")
+        if not self.LO <= T <= self.HI:
+            raise ValueError(f"{self.NAME}: T={T} frames; valid T is {self.LO}..{self.HI}" + self.RANGE_NOTE)
+        if not ops.on_device(x0):
+            raise _lib.HowlHipError(f"{self.NAME} input must be on a HIP device (no CPU fallback)")
+        if x0.dtype != torch.float32:
+            raise ValueError(f"{self.NAME}: features must be fp32")
+        L = self.num_labels
+        cdll = _lib.get().cdll
+        if not cdll.howl_cnn_supported(self.KIND, B, M, T, L):
+            raise _lib.HowlHipError(f"{self.NAME}: B={B}, T={T}, {L} labels is outside the kernels' range (1..64 labels, at most 2^20 rows)")
+        H = self.out_rows(T)
+        ps = self.hot_parameters()
+        b1, b2 = self.encoder1[3], self.encoder2[3]
+        prm = _lib.HowlCnnParams(*[_vp(p) for p in ps])
+        buf = _lib.HowlCnnBuffers(_vp(b1.running_mean), _vp(b1.running_var), _vp(b1.num_batches_tracked), _vp(b2.running_mean),
+                                  _vp(b2.running_var), _vp(b2.num_batches_tracked))
+        ws = torch.empty(cdll.howl_cnn_workspace_bytes(self.KIND, B, T, L), dtype=torch.uint8, device=x0.device)
+        out = torch.empty(self._out_shape(B, H, L), dtype=torch.float32, device=x0.device)
+        mask = self._draw_mask(self._mask_shape(B, H), x0.device) if self.training else None
+        scale = 1.0 / (1.0 - self.dropout_p) if mask is not None else 1.0
+        _lib.get().call("howl_cnn_fwd", self.KIND, ctypes.byref(prm), ctypes.byref(buf), _vp(x0), x0.stride(0), x0.stride(1), x0.stride(2), B,
+                        M, T, L, int(self.training), None if mask is None else _vp(mask), scale, _vp(out), _vp(ws), ws.numel(), ops._stream())
+        self._fwd_version += 1
+        self._cnn_saved = (x0, scale, ws, mask) if self.training else None
+        return self._out_view(out)
+
+    def _launch_backward(self, feat, dout, out_grads=None, ctc_mean=None, adamw=None):
+        """``dout``: d loss / d scores in the scores' shape.  ``ctc_mean`` / ``adamw`` belong to ``SequentialLstm``'s protocol: this
+        model leaves the loss' mean to the loss launch and the optimiser step to the trainer (``optimizer_step_done`` stays False)."""
+        if dout is None:      # FusedTrainer.step_sequence's protocol: (dscores, out_grads=...)
+            raise ValueError(f"{self.NAME}: the backward pass needs d loss / d scores")
+        if ctc_mean is not None:
+            raise NotImplementedError(f"{self.NAME}: the loss' batch mean does not ride in this model's backward (DEFERS_CTC_MEAN is False)")
+        if self._cnn_saved is None:
+            raise NotImplementedError(f"{self.NAME}: the backward pass needs a training-mode forward (eval mode saves nothing)")
+        x0, scale, ws, _ = self._cnn_saved
+        B, M, T = x0.shape
+        ps = self.hot_parameters()
+        grads = out_grads if out_grads is not None else [torch.empty_like(p) for p in ps]
+        prm = _lib.HowlCnnParams(*[_vp(p) for p in ps])
+        gr = _lib.HowlCnnGrads(*[_vp(g) for g in grads])
+        dbuf = self._grad_buffer(dout)
+        _lib.get().call("howl_cnn_bwd", self.KIND, ctypes.byref(prm), _vp(x0), x0.stride(0), x0.stride(1), x0.stride(2), B, M, T,
+                        self.num_labels, scale, _vp(dbuf), ctypes.byref(gr), _vp(ws), ws.numel(), ops._stream())
+        self._cnn_saved = None
+        self.optimizer_step_done = False
+        return grads
+
+    def forward(self, x, lengths=None):
+        return _CnnFunction.apply(self, x, *self.hot_parameters())
+
+
+class SmallCnn(_CnnBase, name="small-cnn"):
+    """``SmallCnn`` of the reference (cnn.py:40-67): a fixed-window classifier, (B, C, 40, T) -> (B, num_labels) for 26 <= T <= 41
+    (the encoder must leave two rows for Linear(384, 128)); T = 40 is the window ``ConvertedStaticModel(model, 40, 10)`` slides."""
+    KIND, NAME = _lib.CNN_SMALL, "small-cnn"
+    CONV0 = ((8, 16), (4, 0), (2, 2))
+    LO, HI = 26, 41
+    RANGE_NOTE = " (the encoder must leave exactly two rows for the head's 384 inputs)"
+
+    @staticmethod
+    def _head_inputs(config):
+        return config.num_hidden_input
+
+    @staticmethod
+    def _mask_shape(B, H):
+        return (B, 128)
+
+    @staticmethod
+    def _out_shape(B, H, L):
+        return (B, L)
+
+    @staticmethod
+    def _out_view(out):
+        return out
+
+    @staticmethod
+    def _grad_buffer(dout):
+        return dout.contiguous()
+
+
+class SequentialCnn(_CnnBase, name="seq-cnn"):
+    """``SequentialCnn`` of the reference (cnn.py:70-104): (B, C, 40, T) -> scores (T', B, num_labels), ``T' = compute_length(T)``,
+    a view of the library's (B, T', num_labels) buffer as for seq-lstm.  ``lengths`` only matter to the CTC loss, which takes
+    ``output_lengths(lengths)``."""
+    KIND, NAME = _lib.CNN_SEQ, "seq-cnn"
+    CONV0 = ((20, 16), (10, 0), (1, 2))
+    LO, HI = 5, 8192
+    RANGE_NOTE = " (fewer than 5 frames leave no output row)"
+    DEFERS_CTC_MEAN = False     # FusedTrainer.step_sequence: the CTC launch writes the batch mean itself
+
+    @staticmethod
+    def _head_inputs(config):
+        return 3 * config.num_maps2
+
+    def compute_length(self, length: int):
+        length = int((length + 2 * 10 - (20 - 1) - 1) / 1 + 1)
+        length //= 2
+        length = int((length + 2 * 2 - (5 - 1) - 1) / 2 + 1)
+        length //= 2
+        return length
+
+    @staticmethod
+    def output_lengths(lengths: torch.Tensor) -> torch.Tensor:
+        """``compute_length`` on a batch of frame counts (int64, any device); at least 0."""
+        n = (lengths.to(torch.int64) + 1) // 2
+        return torch.clamp(((n - 1) // 2 + 1) // 2, min=0)
+
+    @staticmethod
+    def _mask_shape(B, H):
+        return (H, B, 128)
+
+    @staticmethod
+    def _out_shape(B, H, L):
+        return (B, H, L)
+
+    @staticmethod
+    def _out_view(out):
+        return out.permute(1, 0, 2)
+
+    @staticmethod
+    def _grad_buffer(dout):
+        return dout.permute(1, 0, 2).contiguous()      # (no copy for the (T', B, L) view of a (B, T', L) buffer the CTC launch returns)
+
+    def _launch_backward(self, dout, out_grads=None, ctc_mean=None, adamw=None, feat=None):
+        return super()._launch_backward(feat, dout, out_grads=out_grads, ctc_mean=ctc_mean, adamw=adamw)

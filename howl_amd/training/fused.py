@@ -1,5 +1,5 @@
 """Fused training step: frontend -> forward -> loss -> backward -> (RCCL all-reduce) -> AdamW.  Frame objective
-(res8, mobilenet, lstm, gru, las: cross-entropy) and sequence objective (seq-lstm: log_softmax + CTC).
+(res8, mobilenet, lstm, gru, las, small-cnn: cross-entropy) and sequence objective (seq-lstm, seq-cnn: log_softmax + CTC).
 
 This is the loop body of ``training/run/pretrain_gsc.py:124-133`` / ``training/run/train.py:286-302`` with every
 stage a C-ABI call on the current HIP stream, gradients written straight into one flat fp32 buffer (the unit of the
@@ -190,9 +190,16 @@ class FusedTrainer:
         # T > 8192): HowlHipError naming the batch's longest target -- no vendor kernels on the training path
         if "ctc" in kw:      # (already on the device for the fused launch's benefit: no second upload)
             targets, target_lengths = kw["ctc"][0], kw["ctc"][1]
-        loss, dscores, nll, tl_dev = ops.ctc_loss_fwd_bwd(scores, targets, frame_lengths, target_lengths, blank, max_target,
-                                                          defer_mean=True, long_targets=True)
-        ctc_mean = (nll, tl_dev, loss)
+        # the loss takes the model's OUTPUT lengths where the model defines them (seq-cnn: compute_length of the frame counts; the
+        # identity for seq-lstm, which defines none)
+        in_lengths = self.model.output_lengths(frame_lengths) if hasattr(self.model, "output_lengths") else frame_lengths
+        if getattr(self.model, "DEFERS_CTC_MEAN", True):
+            loss, dscores, nll, tl_dev = ops.ctc_loss_fwd_bwd(scores, targets, in_lengths, target_lengths, blank, max_target,
+                                                              defer_mean=True, long_targets=True)
+            ctc_mean = (nll, tl_dev, loss)
+        else:      # a model whose backward carries no rider for the batch mean: the loss launch writes it
+            loss, dscores = ops.ctc_loss_fwd_bwd(scores, targets, in_lengths, target_lengths, blank, max_target, long_targets=True)
+            ctc_mean = None
         # single replica: nothing sits between the backward's gradient fold and the optimiser, so the step rides in the fold
         # (howl_seq_lstm_bwd's HowlAdamW: one launch and one pass over the gradients fewer)
         adamw = None

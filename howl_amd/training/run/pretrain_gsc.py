@@ -23,7 +23,7 @@ from howl_amd.data.collate import DeviceCollate
 from howl_amd.data.transform.operator import ZmuvTransform
 from howl_amd.data.transform.transform import StandardAudioTransform
 from howl_amd.model import RegisteredModel
-from howl_amd.model.cnn import require_supported_mels
+from howl_amd.model.cnn import require_supported_labels, require_supported_mels
 from howl_amd.settings import SETTINGS
 from howl_amd.training.data import ClipBank, load_gsc_splits, read_wav16k, synthetic_bank
 from howl_amd.training.fused import FusedTrainer
@@ -96,6 +96,7 @@ def main(argv=None):
     zmuv_transform = ZmuvTransform().to(device)
     model = RegisteredModel.find_registered_class(args.model)(num_labels).to(device)
     require_supported_mels(model)      # res8 with NUM_MELS other than 40 / 80: an error here, not at the first batch
+    require_supported_labels(model)    # small-cnn / seq-cnn size their head from NUM_LABELS, not from the label space
     params = [p for p in model.parameters() if p.requires_grad]
     logging.info(f"{sum(p.numel() for p in params)} parameters")
 
@@ -148,7 +149,7 @@ def main(argv=None):
     workspace.save_settings(SETTINGS)
     writer.add_scalar("Meta/Parameters", sum(p.numel() for p in params))
     if not hasattr(model, "hot_parameters"):
-        raise NotImplementedError(f"{args.model}: no fused MI355X training step (res8, mobilenet, lstm, gru, las have one)")
+        raise NotImplementedError(f"{args.model}: no fused MI355X training step (res8, mobilenet, lstm, gru, las, small-cnn have one)")
     trainer = FusedTrainer(model, std_transform, zmuv_transform, SETTINGS.training.learning_rate,
                            weight_decay=SETTINGS.training.weight_decay)
     trainer.broadcast_parameters()                                     # rank 0's initial weights and BatchNorm buffers
