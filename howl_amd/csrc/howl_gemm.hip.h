@@ -1,6 +1,7 @@
-// Shared dense building blocks of the LSTM and MobileNet paths (included by lstm.hip and mobilenet.hip; every
-// translation unit gets its own copy in an anonymous namespace): the generic fp32 MFMA GEMM with row maps and
-// split-K, deterministic slab / column sums, and their host-side launch helpers.
+// Shared dense building blocks of the LSTM, GRU, LAS, CNN and MobileNet paths (included by lstm.hip, gru.hip, las.hip, cnn.hip,
+// mobilenet.hip and -- as the tests' door, include/howl_hip_dense.h -- dense.hip; every translation unit gets its own copy in an
+// anonymous namespace): the generic fp32 MFMA GEMM with row maps and split-K, deterministic slab / column sums, and their
+// host-side launch helpers.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -9,6 +10,36 @@
 #include "howl_common.hip.h"
 
 namespace {
+
+// Choice record: every host helper below notes which kernel instance it launched (or collected) -- family, template arguments,
+// grid, k-per-split -- in a small per-thread log of this translation unit.  One host store per launch; nobody but dense.hip
+// (howl_dense_choices) reads it or resets it, so in the other translation units it fills up once and stays.
+enum DenseFamily {
+    DC_GEMM = 1,           // gemm_kernel<t0 = A_MAJOR_IS_K>
+    DC_GEMM_VEC = 2,       // gemm_vec_kernel<t0 = A_UNIT_K, t1 = B_UNIT_K, t2 = KMAP_LIN>
+    DC_ROWGEMM = 3,        // rowgemm_kernel<t0 = KG, t1 = NT, t2 = W_UNIT_K, t3 = NO2>
+    DC_THIN_WGRAD = 4,     // thin_wgrad_kernel<t0 = NO>; kps = rows per chunk
+    DC_WGRAD_BIG = 5,      // wgrad_big_kernel<t0 = TN, t1 = KMAP_LIN>
+    DC_WGRAD_JOB = 6,      // a job collected for wgrad_big_multi_kernel: t0 = tn (64, 128, 192 = dual), t1 = klin
+    DC_WGRAD_MULTI = 7,    // wgrad_big_multi_kernel's launch: t0 = jobs, gx = blocks
+    DC_WGRAD_W8 = 8,       // wgrad_w8_body in a 512-thread kernel (noted by that kernel's launcher)
+    DC_SUM_SLABS = 9,      // sum_slabs_kernel: kps = nparts
+    DC_SUM_SLABS_MULTI = 10,  // sum_slabs_multi_kernel: t0 = jobs, t1 = AdamW rider, t2 = mean rider
+    DC_COLSUM = 11,        // colsum_kernel: kps = rows per chunk
+    DC_RELU_BWD = 12,      // relu_bwd_kernel (noted by its launcher)
+};
+struct DenseChoice {
+    int family, t0, t1, t2, t3, gx, gy, gz, kps;
+};
+constexpr int DENSE_LOG_MAX = 16;
+struct DenseChoiceLog {
+    DenseChoice e[DENSE_LOG_MAX];
+    int n;
+};
+thread_local DenseChoiceLog dense_log{};
+inline void dense_note(int family, int t0, int t1, int t2, int t3, dim3 g, int kps) {
+    if (dense_log.n < DENSE_LOG_MAX) dense_log.e[dense_log.n++] = DenseChoice{family, t0, t1, t2, t3, (int)g.x, (int)g.y, (int)g.z, kps};
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // Generic fp32 MFMA GEMM:  C[m][n] = sum_k A(m,k) * B(k,n)  (+ bias[n]) (ReLU)
@@ -627,6 +658,7 @@ struct SlabSums {
         }
         if (count == 0 && mean.nll == nullptr) return true;
         const int rider = mean.nll != nullptr ? 1 : 0;
+        dense_note(DC_SUM_SLABS_MULTI, count, opt != nullptr && opt->on ? 1 : 0, rider, 0, dim3((unsigned)std::max<long>((max_n + 63) / 64, 1), count + rider), 0);
         hipLaunchKernelGGL(sum_slabs_multi_kernel, dim3((unsigned)std::max<long>((max_n + 63) / 64, 1), count + rider), dim3(256), 0, s, jobs,
                            opt != nullptr ? *opt : SlabAdamW{nullptr, nullptr, nullptr, nullptr, HowlAdamWCoef{}, 0}, mean, count);
         count = 0;
@@ -697,6 +729,7 @@ int gemm(hipStream_t s, bool a_major_k, const float* a, RowMap am, long a_ks, Ro
             const int blocks = std::min(ntiles, howl_num_cus());
 #define HOWL_ROWGEMM(KG_, NT_)                                                                                                \
     do {                                                                                                                      \
+        dense_note(DC_ROWGEMM, KG_, NT_, w_unit_k ? 1 : 0, 0, dim3(blocks), 0);                                               \
         if (w_unit_k)                                                                                                         \
             hipLaunchKernelGGL((rowgemm_kernel<KG_, NT_, true>), dim3(blocks), dim3(RG_THREADS), 0, s, a, am, b, w_stride, M, K, \
                                bias, relu, c, c_ms, RowGemmThin{});                                                           \
@@ -719,6 +752,7 @@ int gemm(hipStream_t s, bool a_major_k, const float* a, RowMap am, long a_ks, Ro
                     HOWL_ROWGEMM_THIN(6) HOWL_ROWGEMM_THIN(7) HOWL_ROWGEMM_THIN(8)
                 }
 #undef HOWL_ROWGEMM_THIN
+                dense_note(DC_ROWGEMM, 8, 2, 1, thin_out, dim3(blocks), 0);
                 *thin_done = true;
                 return 1;
             }
@@ -757,6 +791,7 @@ int gemm(hipStream_t s, bool a_major_k, const float* a, RowMap am, long a_ks, Ro
             else if (b_unit_k) HOWL_GEMM_VEC(false, true);
             else HOWL_GEMM_VEC(false, false);
 #undef HOWL_GEMM_VEC
+            dense_note(DC_GEMM_VEC, a_major_k ? 1 : 0, b_unit_k ? 1 : 0, klin ? 1 : 0, 0, grid, kps);
             return (int)grid.z;
         }
     }
@@ -766,6 +801,7 @@ int gemm(hipStream_t s, bool a_major_k, const float* a, RowMap am, long a_ks, Ro
     else
         hipLaunchKernelGGL(gemm_kernel<false>, grid, dim3(256), 0, s, a, am, a_ks, ak, b, bk, b_ns, M, N, K, kps, bias, relu,
                            c, c_ms, c_split_stride);
+    dense_note(DC_GEMM, a_major_k ? 1 : 0, 0, 0, 0, grid, kps);
     return (int)grid.z;
 }
 
@@ -1164,6 +1200,7 @@ inline void wgrad_jobs_flush(hipStream_t s, WgradJobs& jobs) {
     int blocks = 0;
     for (int q = 0; q < jobs.count; ++q) blocks += jobs.j[q].gx * jobs.j[q].gy * jobs.j[q].gz;
     HowlProfScope prof("gemm", s, jobs.flops);
+    dense_note(DC_WGRAD_MULTI, jobs.count, 0, 0, 0, dim3(blocks), 0);
     hipLaunchKernelGGL(wgrad_big_multi_kernel, dim3(blocks), dim3(WG_THREADS), 0, s, jobs);
     jobs.count = 0;
     jobs.flops = 0.0;
@@ -1197,11 +1234,13 @@ void wgrad_gemm(hipStream_t s, const float* dout, RowMap dm, int n_out, const fl
             HOWL_THIN(1) HOWL_THIN(2) HOWL_THIN(3) HOWL_THIN(4) HOWL_THIN(5) HOWL_THIN(6) HOWL_THIN(7) HOWL_THIN(8)
         }
 #undef HOWL_THIN
+        dense_note(DC_THIN_WGRAD, n_out, 0, 0, 0, grid, rpc);
         const long n = (long)n_out * k_in;
         if (defer != nullptr) {
             defer->add(scratch, chunks, n, dw);
             return;
         }
+        dense_note(DC_SUM_SLABS, 0, 0, 0, 0, dim3((unsigned)((n + 63) / 64)), chunks);
         hipLaunchKernelGGL(sum_slabs_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, (const float*)scratch, chunks, n, dw);
         return;
     }
@@ -1224,10 +1263,12 @@ void wgrad_gemm(hipStream_t s, const float* dout, RowMap dm, int n_out, const fl
             jobs->j[jobs->count++] = WgradJob{dout, dm, in, im, n_out, k_in, rows, kps, scratch, (int)grid.x, (int)grid.y, (int)grid.z, tn, klin ? 1 : 0,
                                               WgradSecond{nullptr, RowMap{1, 0, 0}, 0, nullptr}};
             jobs->flops += 2.0 * (double)n_out * k_in * rows;
+            dense_note(DC_WGRAD_JOB, tn, klin ? 1 : 0, 0, 0, grid, kps);
             defer->add(scratch, z, (long)n_out * k_in, dw);
             return;
         }
         HowlProfScope prof("gemm", s, 2.0 * (double)n_out * k_in * rows);
+        dense_note(DC_WGRAD_BIG, tn, klin ? 1 : 0, 0, 0, grid, kps);
         if (tn == 128) {
             if (klin) hipLaunchKernelGGL((wgrad_big_kernel<128, true>), grid, dim3(WG_THREADS), 0, s, dout, dm, in, im, n_out, k_in, rows, kps, scratch);
             else hipLaunchKernelGGL((wgrad_big_kernel<128, false>), grid, dim3(WG_THREADS), 0, s, dout, dm, in, im, n_out, k_in, rows, kps, scratch);
@@ -1244,6 +1285,7 @@ void wgrad_gemm(hipStream_t s, const float* dout, RowMap dm, int n_out, const fl
         defer->add(scratch, z, n, dw);
         return;
     }
+    dense_note(DC_SUM_SLABS, 0, 0, 0, 0, dim3((unsigned)((n + 63) / 64)), z);
     hipLaunchKernelGGL(sum_slabs_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, (const float*)scratch, z, n, dw);
 }
 
@@ -1267,6 +1309,7 @@ bool wgrad_dual_gemm(const float* dout, RowMap dm, int n_out, const float* in, R
     const int z = (rows + kps - 1) / kps;
     jobs->j[jobs->count++] = WgradJob{dout, dm, in, im, n_out, 128, rows, kps, scratch, 1, tiles, z, 192, 0, WgradSecond{in2, im2, k2, scratch2}};
     jobs->flops += 2.0 * (double)n_out * (128 + k2) * rows;
+    dense_note(DC_WGRAD_JOB, 192, 0, 0, 0, dim3(1, tiles, z), kps);
     defer->add(scratch, z, (long)n_out * 128, dw);
     defer->add(scratch2, z, (long)n_out * k2, dw2);
     return true;
@@ -1278,12 +1321,15 @@ void colsum(hipStream_t s, const float* x, RowMap rm, int rows, int n, float* sc
     int chunks = rows / rows_per_chunk;
     chunks = chunks < 1 ? 1 : (chunks > max_chunks ? max_chunks : chunks);   // scratch holds <= max_chunks slabs of n floats
     const int rpc = (rows + chunks - 1) / chunks;
+    dense_note(DC_COLSUM, 0, 0, 0, 0, dim3((n + 63) / 64, chunks), rpc);
     hipLaunchKernelGGL(colsum_kernel, dim3((n + 63) / 64, chunks), dim3(256), 0, s, x, rm, rows, n, rpc, scratch);
     if (defer != nullptr) {
         defer->add(scratch, chunks, n, out0, out1);
         return;
     }
+    dense_note(DC_SUM_SLABS, 0, 0, 0, 0, dim3((n + 63) / 64), chunks);
     hipLaunchKernelGGL(sum_slabs_kernel, dim3((n + 63) / 64), dim3(256), 0, s, (const float*)scratch, chunks, (long)n, out0);
+    if (out1 != nullptr) dense_note(DC_SUM_SLABS, 0, 0, 0, 0, dim3((n + 63) / 64), chunks);
     if (out1 != nullptr)
         hipLaunchKernelGGL(sum_slabs_kernel, dim3((n + 63) / 64), dim3(256), 0, s, (const float*)scratch, chunks, (long)n, out1);
 }

@@ -130,6 +130,33 @@ class HowlCnnBuffers(ctypes.Structure):
     _fields_ = [(n, P) for n in ("bn1_mean", "bn1_var", "bn1_batches", "bn2_mean", "bn2_var", "bn2_batches")]
 
 
+class HowlDenseRowMap(ctypes.Structure):
+    """``HowlDenseRowMap`` of ``include/howl_hip_dense.h``; ``inner = DENSE_LIN`` is the plain stride ``s_inner``."""
+    _fields_ = [("inner", c_int), ("s_outer", c_long), ("s_inner", c_long)]
+
+
+class HowlDenseChoice(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("family", "t0", "t1", "t2", "t3", "gx", "gy", "gz", "kps")]
+
+
+class HowlDenseGemm(ctypes.Structure):
+    _fields_ = [("a_major_k", c_int), ("a", P), ("am", HowlDenseRowMap), ("a_ks", c_long), ("ak", HowlDenseRowMap), ("b", P),
+                ("bk", HowlDenseRowMap), ("b_ns", c_long), ("M", c_int), ("N", c_int), ("K", c_int), ("splits", c_int), ("bias", P),
+                ("relu", c_int), ("c", P), ("c_ms", c_long), ("c_split_stride", c_long), ("c_floats", c_size_t), ("w2", P), ("b2", P),
+                ("y2", P), ("thin_out", c_int)]
+
+
+class HowlDenseWgrad(ctypes.Structure):
+    _fields_ = [("dout", P), ("dm", HowlDenseRowMap), ("n_out", c_int), ("in_", P), ("im", HowlDenseRowMap), ("k_in", c_int),
+                ("rows", c_int), ("scratch", P), ("scratch_floats", c_size_t), ("dw", P), ("max_splits", c_int),
+                ("rows_per_split", c_int), ("in2", P), ("im2", HowlDenseRowMap), ("k2", c_int), ("scratch2", P),
+                ("scratch2_floats", c_size_t), ("dw2", P)]
+
+
+class HowlDenseSlabJob(ctypes.Structure):
+    _fields_ = [("part", P), ("nparts", c_int), ("stride", c_long), ("n", c_long), ("out", P), ("out2", P)]
+
+
 class HowlDecideConfig(ctypes.Structure):
     """``HowlDecideConfig`` of ``include/howl_hip_decide.h``: a host struct; ``weights`` / ``color`` are device pointers."""
     _fields_ = [("mode", c_int), ("C", c_int), ("blank", c_int), ("negative", c_int), ("threshold", c_double), ("smoothing_ms", c_double),
@@ -279,6 +306,26 @@ TIMESTRETCH_MIN_SAMPLES = 2048                                                  
 STRETCH_CLIP_FIELDS = [("rate", "<f8"), ("src_row", "<i8"), ("dst_off", "<i8"), ("len", "<i4"), ("out_len", "<i4"), ("n_out", "<i4"),
                        ("bg_idx", "<i4"), ("bg_off", "<i4"), ("alpha", "<f4")]
 
+# The tests' door to the dense kernels of ``howl_gemm.hip.h``: ``include/howl_hip_dense.h`` (``tests/test_emu_dense.py`` checks the
+# tables against that header)
+DENSE_LIN = 1 << 30                                                                 # HOWL_DENSE_LIN
+DENSE_FAMILIES = {1: "gemm_kernel", 2: "gemm_vec_kernel", 3: "rowgemm_kernel", 4: "thin_wgrad_kernel", 5: "wgrad_big_kernel",
+                  6: "wgrad_big_multi_kernel.job", 7: "wgrad_big_multi_kernel", 8: "wgrad_w8_body", 9: "sum_slabs_kernel",
+                  10: "sum_slabs_multi_kernel", 11: "colsum_kernel", 12: "relu_bwd_kernel"}
+DENSE_SIGNATURES = {
+    "howl_dense_gemm": [POINTER(HowlDenseGemm), POINTER(c_int), POINTER(c_int), STREAM],
+    "howl_dense_wgrad": [c_int, c_int, POINTER(HowlDenseWgrad), STREAM],
+    "howl_dense_wgrad_slabs": [POINTER(HowlDenseWgrad), c_int, POINTER(c_int), STREAM],
+    "howl_dense_colsum": [P, POINTER(HowlDenseRowMap), c_int, c_int, P, c_size_t, P, P, c_int, c_int, c_int, STREAM],
+    "howl_dense_slab_sums": [c_int, POINTER(HowlDenseSlabJob), POINTER(HowlAdamW), POINTER(HowlCtcMean), STREAM],
+    "howl_dense_sum_slabs": [P, c_int, c_long, P, STREAM],
+    "howl_dense_relu_bwd": [P, P, c_long, P, STREAM],
+}
+DENSE_SIZE_FUNCS = {"howl_dense_choices": [POINTER(HowlDenseChoice), c_size_t], "howl_dense_num_cus": [],
+                    "howl_dense_gemm_splits": [c_int, c_int], "howl_dense_gemm_c_floats": [POINTER(HowlDenseGemm)],
+                    "howl_dense_wgrad_splits": [POINTER(HowlDenseWgrad)], "howl_dense_wgrad_scratch_floats": [POINTER(HowlDenseWgrad)],
+                    "howl_dense_wgrad_scratch2_floats": [POINTER(HowlDenseWgrad)], "howl_dense_colsum_chunks": [c_int, c_int, c_int]}
+
 
 class HowlHipError(RuntimeError):
     pass
@@ -296,13 +343,14 @@ class Library:
         self.cdll.howl_last_error.restype = c_char_p
         self.cdll.howl_last_error.argtypes = []
         for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES, **LSTM_STREAM_SIGNATURES, **DECIDE_SIGNATURES,
-                               **CTC_LONG_SIGNATURES, **GRU_SIGNATURES, **LAS_SIGNATURES, **TIMESTRETCH_SIGNATURES, **CNN_SIGNATURES}.items():
+                               **CTC_LONG_SIGNATURES, **GRU_SIGNATURES, **LAS_SIGNATURES, **TIMESTRETCH_SIGNATURES, **CNN_SIGNATURES,
+                               **DENSE_SIGNATURES}.items():
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = c_int
             fn.argtypes = argtypes
         for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS, **LSTM_STREAM_SIZE_FUNCS, **DECIDE_SIZE_FUNCS,
                                **CTC_LONG_SIZE_FUNCS, **GRU_SIZE_FUNCS, **LAS_SIZE_FUNCS, **TIMESTRETCH_SIZE_FUNCS,
-                               **CNN_SIZE_FUNCS}.items():
+                               **CNN_SIZE_FUNCS, **DENSE_SIZE_FUNCS}.items():
             fn = getattr(self.cdll, name)
             fn.restype = c_size_t
             fn.argtypes = argtypes
