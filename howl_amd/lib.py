@@ -283,6 +283,15 @@ LAS_SIGNATURES = {
 }
 LAS_SIZE_FUNCS = {"howl_las_supported": [c_int, c_int, c_int, c_int], "howl_las_workspace_bytes": [c_int, c_int]}
 
+# The streaming las entry points of ``include/howl_hip_las_stream.h`` (tables of their own: ``tests/test_emu_las_stream.py`` checks
+# them against that header)
+LAS_STREAM_SIGNATURES = {
+    "howl_las_stream_prepare": [POINTER(HowlLasParams), POINTER(HowlLasBuffers), c_int, P, c_size_t, STREAM],
+    "howl_las_stream_windows": [P, P, c_long, c_int, c_int, c_int, P, c_int, c_float, P, c_int, P, P, P, c_size_t, STREAM],
+}
+LAS_STREAM_SIZE_FUNCS = {"howl_las_stream_supported": [c_int, c_int, c_int], "howl_las_stream_state_bytes": [c_int],
+                         "howl_las_stream_workspace_bytes": [c_int, c_int]}
+
 # The small-cnn / seq-cnn entry points of ``include/howl_hip_cnn.h`` (``tests/test_emu_cnn.py`` checks them against that header)
 CNN_SMALL, CNN_SEQ = 0, 1                                                           # HOWL_CNN_SMALL, HOWL_CNN_SEQ
 CNN_SIGNATURES = {
@@ -343,14 +352,14 @@ class Library:
         self.cdll.howl_last_error.restype = c_char_p
         self.cdll.howl_last_error.argtypes = []
         for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES, **LSTM_STREAM_SIGNATURES, **DECIDE_SIGNATURES,
-                               **CTC_LONG_SIGNATURES, **GRU_SIGNATURES, **LAS_SIGNATURES, **TIMESTRETCH_SIGNATURES, **CNN_SIGNATURES,
-                               **DENSE_SIGNATURES}.items():
+                               **CTC_LONG_SIGNATURES, **GRU_SIGNATURES, **LAS_SIGNATURES, **LAS_STREAM_SIGNATURES,
+                               **TIMESTRETCH_SIGNATURES, **CNN_SIGNATURES, **DENSE_SIGNATURES}.items():
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = c_int
             fn.argtypes = argtypes
         for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS, **LSTM_STREAM_SIZE_FUNCS, **DECIDE_SIZE_FUNCS,
-                               **CTC_LONG_SIZE_FUNCS, **GRU_SIZE_FUNCS, **LAS_SIZE_FUNCS, **TIMESTRETCH_SIZE_FUNCS,
-                               **CNN_SIZE_FUNCS, **DENSE_SIZE_FUNCS}.items():
+                               **CTC_LONG_SIZE_FUNCS, **GRU_SIZE_FUNCS, **LAS_SIZE_FUNCS, **LAS_STREAM_SIZE_FUNCS,
+                               **TIMESTRETCH_SIZE_FUNCS, **CNN_SIZE_FUNCS, **DENSE_SIZE_FUNCS}.items():
             fn = getattr(self.cdll, name)
             fn.restype = c_size_t
             fn.argtypes = argtypes

@@ -20,8 +20,8 @@ from howl_amd.settings import _EnvSettings
 
 from .base import RegisteredModel
 
-__all__ = ["FixedAttentionModuleConfig", "LASClassifier", "LASClassifierConfig", "LASEncoderConfig", "LstmConfig", "LstmStreamSession",
-           "SequentialLstm", "SimpleGru", "SimpleLstm"]
+__all__ = ["FixedAttentionModuleConfig", "LASClassifier", "LASClassifierConfig", "LASEncoderConfig", "LasStreamSession", "LstmConfig",
+           "LstmStreamSession", "SequentialLstm", "SimpleGru", "SimpleLstm"]
 
 HID = 128
 
@@ -654,6 +654,72 @@ class _LasFunction(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads)
 
 
+class LasStreamSession:
+    """Streaming las: ``probabilities(pcm)`` takes (N, L) raw PCM windows to their (N, C) class probabilities in ONE kernel launch
+    (``howl_las_stream_windows``: log-mel, deltas and ZMUV, both convolutions, the input projections, both recurrences, the
+    attention, the head and the softmax, one workgroup per window).  The session owns its prepared state (W_ih and the V / K
+    projections as MFMA fragments, W_hh in lane order, both BatchNorms folded from their running statistics) and its scratch, so
+    two engines on two streams share nothing; the state is prepared again whenever a hot parameter, a BatchNorm weight or bias or
+    a running buffer of the model was replaced or written through torch since the last launch (``data_ptr()`` / ``_version``:
+    ``load_state_dict``, an optimiser step).  Writes that torch does not see need ``refresh()``.  Eval mode only, standard
+    filterbank only."""
+
+    def __init__(self, model, std, zmuv):
+        self.model, self.std, self.zmuv = model, std, zmuv
+        self._state = None
+        self._key = None
+        self._ws = None
+        self._frames = {}
+
+    def supported(self, n_samples: int) -> bool:
+        """Windows of ``n_samples`` samples are inside the kernel's range (40 mel bins, 512 samples .. 83 frames, <= 64 labels) and
+        the frontend would not draw a VTLP filterbank for them."""
+        vtlp = self.std.augment_params[0].enabled and self.std.training
+        return not vtlp and ops.las_stream_supported(n_samples, self.std.n_mels, self.model.num_labels)
+
+    def refresh(self):
+        """Forces the next call to prepare the state again."""
+        self._key = None
+
+    def _watched(self):
+        bn1, bn2 = self.model.encoder.conv_encoder[1], self.model.encoder.conv_encoder[5]
+        return self.model.hot_parameters() + [bn1.running_mean, bn1.running_var, bn2.running_mean, bn2.running_var]
+
+    def _prepared_state(self, device):
+        key = tuple((t.data_ptr(), t._version) for t in self._watched())
+        if self._state is None or self._state.device != device or key != self._key:
+            if self._state is None or self._state.device != device:
+                self._state = torch.empty(ops.las_stream_state_bytes(self.model.num_labels), dtype=torch.uint8, device=device)
+            prm = _lib.HowlLasParams(*[_vp(p) for p in self.model.hot_parameters()])
+            ops.las_stream_prepare(prm, self.model._bn_buffers(), self.model.num_labels, self._state)
+            self._key = key
+        return self._state
+
+    @torch.no_grad()
+    def probabilities(self, pcm: torch.Tensor, frames: int = None, logits: torch.Tensor = None) -> torch.Tensor:
+        """pcm: (N, L) fp32 on the device, unit sample stride (rows may be overlapping views of one clip); ``frames``: the frames the
+        recurrences and the attention run over (None: ``std.compute_lengths(L)``) -> (N, C) on the device."""
+        if self.model.training:
+            raise RuntimeError("LasStreamSession runs eval-mode BatchNorm (running statistics) and no dropout: call model.eval() first")
+        if pcm.dim() != 2 or not self.supported(pcm.size(1)):
+            raise ValueError(f"LasStreamSession: windows of shape {tuple(pcm.shape)} are outside the streaming kernel's range "
+                             f"(see supported()); use the model's forward")
+        if self.std.augment_params[0].enabled:
+            self.std.rand.random()      # the frontend's draw happens on every call, eval mode included: keep the stream's position
+        N, L = pcm.shape
+        if frames is None:      # (it depends on the window's size alone: computed once per size)
+            if L not in self._frames:
+                self._frames[L] = int(self.std.compute_lengths(torch.tensor([L]))[0])
+            frames = self._frames[L]
+        state = self._prepared_state(pcm.device)
+        need = ops.las_stream_workspace_bytes(N, L)
+        if self._ws is None or self._ws.device != pcm.device or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=pcm.device)
+        pair = self.zmuv.pair() if self.zmuv is not None else None
+        return ops.las_stream_windows(state, pcm, int(frames), self.std._standard_fb(), self.std.n_mels, pair, self.model.num_labels,
+                                      self._ws, logits=logits)
+
+
 class _LasEncoder(nn.Module):
     """Parameter container with the reference's names (rnn.py:133-153): conv1 and conv2 are registered twice, as attributes and
     inside ``conv_encoder``, so both key families appear in the ``state_dict`` and share one tensor each."""
@@ -821,3 +887,8 @@ class LASClassifier(RegisteredModel, name="las"):
 
     def forward(self, x, lengths):
         return _LasFunction.apply(self, x, lengths, None, *self.hot_parameters())
+
+    def stream_session(self, std, zmuv) -> LasStreamSession:
+        """A streaming session over this model, ``std`` (a ``StandardAudioTransform``) and ``zmuv`` (a ``ZmuvTransform`` or None):
+        raw PCM windows -> probabilities in one launch, with buffers of its own (``LasStreamSession``)."""
+        return LasStreamSession(self, std, zmuv)

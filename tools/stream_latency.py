@@ -7,6 +7,8 @@ in one process, on one card.  In addition, for N = 64 and N = 256 windows per la
 between two HIP events beside ``engine.window_probabilities`` on the same windows (wall time, host copy included: what that call
 is).  Prints one JSON line.  ``--windows`` / ``--repeats`` shorten a run (a profiler pass); the protocol is the default.
 
+``--model las``: the same protocol for the las model (LasStreamSession), with the launch alone at N = 1 as well.
+
 ``--model seq-lstm``: the same protocol for ``InferenceEngine.infer`` (LstmStreamSession): (a) 8000-sample chunks (what the live
 client feeds), (b) 16000-sample chunks, both with the state carried from call to call; (c) ``infer_many`` on 64 clips of 1 - 3 s
 against the clip-by-clip ``[reset(); infer(clip)]`` loop (per CALL of 64 clips; ``--windows`` / 20 calls per repeat); and the
@@ -38,7 +40,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--fused-only", action="store_true", help="skip the eager path (a kernel-trace pass over the one launch)")
     ap.add_argument("--eager-only", action="store_true", help="seq-lstm: skip the fused path (a kernel-trace pass over the launch chain)")
-    ap.add_argument("--model", choices=["res8", "seq-lstm", "decide"], default="res8")
+    ap.add_argument("--model", choices=["res8", "las", "seq-lstm", "decide"], default="res8")
     args = ap.parse_args()
     if args.model == "seq-lstm":
         return main_seq_lstm(args)
@@ -54,8 +56,12 @@ def main():
     from howl_amd.utils.synth import res8_closed_form_state, synthetic_pcm
     dev = torch.device("cuda:0")
     ctx = InferenceContext(["hey", "fire", "fox"], token_type="word", use_blank=False)
-    model = RegisteredModel.find_registered_class("res8")(ctx.num_labels).to(dev)
-    model.load_state_dict(res8_closed_form_state(ctx.num_labels), strict=False)
+    if args.model == "las":
+        torch.manual_seed(2024)
+        model = RegisteredModel.find_registered_class("las")(ctx.num_labels).to(dev)
+    else:
+        model = RegisteredModel.find_registered_class("res8")(ctx.num_labels).to(dev)
+        model.load_state_dict(res8_closed_form_state(ctx.num_labels), strict=False)
     model.eval()
     std = StandardAudioTransform().to(dev).eval()
     zmuv = ZmuvTransform().to(dev)
@@ -86,7 +92,7 @@ def main():
 
     many = []
     session = model.stream_session(std, zmuv)
-    for n in (64, 256):
+    for n in ((1, 64, 256) if args.model == "las" else (64, 256)):
         stride = (160000 - chunk) // n // 2 * 2
         clip = clips[0, :chunk + (n - 1) * stride].contiguous()
         windows = clip.as_strided((n, chunk), (stride, 1))
@@ -99,7 +105,7 @@ def main():
             e1.synchronize()
             fused_us.append(e0.elapsed_time(e1) * 1e3)
         row = {"windows_per_launch": n, "fused_launch_us_median": round(statistics.median(fused_us[10:]), 2)}
-        if not args.fused_only:
+        if not args.fused_only and n > 1:
             eng = FrameInferenceEngine(500, 1000.0 * stride / 16000 + 1e-6, model, zmuv, ctx)
             assert audio_utils.stride_starts(clip.numel(), 500, eng.eval_stride_size_ms, 16000)[0] == [stride * k for k in range(n)]
             eager_us = []
@@ -120,6 +126,7 @@ def main():
     torch.cuda.synchronize()
     fused_m, eager_m = medians[True], medians[False]
     print(json.dumps({
+        "model": args.model,
         "metric": "ingest_frame wall time per window, us (500 ms windows, 63 ms stride, 10 s synthetic clips; median of each repeat)",
         "windows_per_repeat": args.windows, "warmup_windows": args.warmup,
         "fused_us_medians": [round(v, 2) for v in fused_m], "eager_us_medians": [round(v, 2) for v in eager_m],
