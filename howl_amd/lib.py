@@ -292,6 +292,14 @@ LAS_STREAM_SIGNATURES = {
 LAS_STREAM_SIZE_FUNCS = {"howl_las_stream_supported": [c_int, c_int, c_int], "howl_las_stream_state_bytes": [c_int],
                          "howl_las_stream_workspace_bytes": [c_int, c_int]}
 
+# The streaming gru entry points of ``include/howl_hip_gru_stream.h`` (tables of their own: ``tests/test_emu_gru_stream.py`` checks
+# them against that header)
+GRU_STREAM_SIGNATURES = {
+    "howl_gru_stream_windows": [POINTER(HowlGruParams), POINTER(HowlGruBuffers), P, c_long, c_int, c_int, c_int, P, c_int, c_float, P, c_int,
+                                P, P, P, c_size_t, STREAM],
+}
+GRU_STREAM_SIZE_FUNCS = {"howl_gru_stream_supported": [c_int, c_int, c_int], "howl_gru_stream_workspace_bytes": [c_int, c_int]}
+
 # The small-cnn / seq-cnn entry points of ``include/howl_hip_cnn.h`` (``tests/test_emu_cnn.py`` checks them against that header)
 CNN_SMALL, CNN_SEQ = 0, 1                                                           # HOWL_CNN_SMALL, HOWL_CNN_SEQ
 CNN_SIGNATURES = {
@@ -353,13 +361,13 @@ class Library:
         self.cdll.howl_last_error.argtypes = []
         for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES, **LSTM_STREAM_SIGNATURES, **DECIDE_SIGNATURES,
                                **CTC_LONG_SIGNATURES, **GRU_SIGNATURES, **LAS_SIGNATURES, **LAS_STREAM_SIGNATURES,
-                               **TIMESTRETCH_SIGNATURES, **CNN_SIGNATURES, **DENSE_SIGNATURES}.items():
+                               **GRU_STREAM_SIGNATURES, **TIMESTRETCH_SIGNATURES, **CNN_SIGNATURES, **DENSE_SIGNATURES}.items():
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = c_int
             fn.argtypes = argtypes
         for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS, **LSTM_STREAM_SIZE_FUNCS, **DECIDE_SIZE_FUNCS,
                                **CTC_LONG_SIZE_FUNCS, **GRU_SIZE_FUNCS, **LAS_SIZE_FUNCS, **LAS_STREAM_SIZE_FUNCS,
-                               **TIMESTRETCH_SIZE_FUNCS, **CNN_SIZE_FUNCS, **DENSE_SIZE_FUNCS}.items():
+                               **GRU_STREAM_SIZE_FUNCS, **TIMESTRETCH_SIZE_FUNCS, **CNN_SIZE_FUNCS, **DENSE_SIZE_FUNCS}.items():
             fn = getattr(self.cdll, name)
             fn.restype = c_size_t
             fn.argtypes = argtypes

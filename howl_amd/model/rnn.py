@@ -20,8 +20,8 @@ from howl_amd.settings import _EnvSettings
 
 from .base import RegisteredModel
 
-__all__ = ["FixedAttentionModuleConfig", "LASClassifier", "LASClassifierConfig", "LASEncoderConfig", "LasStreamSession", "LstmConfig",
-           "LstmStreamSession", "SequentialLstm", "SimpleGru", "SimpleLstm"]
+__all__ = ["FixedAttentionModuleConfig", "GruStreamSession", "LASClassifier", "LASClassifierConfig", "LASEncoderConfig",
+           "LasStreamSession", "LstmConfig", "LstmStreamSession", "SequentialLstm", "SimpleGru", "SimpleLstm"]
 
 HID = 128
 
@@ -513,6 +513,49 @@ class _GruFunction(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads)
 
 
+class GruStreamSession:
+    """Streaming gru: ``probabilities(pcm)`` takes (N, L) raw PCM windows to their (N, C) class probabilities in ONE kernel launch
+    (``howl_gru_stream_windows``: log-mel and ZMUV, both convolutions, the recurrence, the head and the softmax, one workgroup per
+    window).  The kernel reads the model's parameters and running statistics in place, so there is no prepared state and nothing
+    to refresh: a ``load_state_dict``, an optimiser step or a write torch does not see is in the next call's answer.  The session
+    owns its scratch, so two engines on two streams share nothing.  Eval mode only, standard filterbank only."""
+
+    def __init__(self, model, std, zmuv):
+        self.model, self.std, self.zmuv = model, std, zmuv
+        self._ws = None
+        self._frames = {}
+
+    def supported(self, n_samples: int) -> bool:
+        """Windows of ``n_samples`` samples are inside the kernel's range (40 mel bins, 512 samples .. 83 frames, <= 64 labels) and
+        the frontend would not draw a VTLP filterbank for them."""
+        vtlp = self.std.augment_params[0].enabled and self.std.training
+        return not vtlp and ops.gru_stream_supported(n_samples, self.std.n_mels, self.model.num_labels)
+
+    @torch.no_grad()
+    def probabilities(self, pcm: torch.Tensor, frames: int = None, logits: torch.Tensor = None) -> torch.Tensor:
+        """pcm: (N, L) fp32 on the device, unit sample stride (rows may be overlapping views of one clip); ``frames``: the frames the
+        recurrence runs over (None: ``std.compute_lengths(L)``) -> (N, C) on the device."""
+        if self.model.training:
+            raise RuntimeError("GruStreamSession runs eval-mode BatchNorm (running statistics) and no dropout: call model.eval() first")
+        if pcm.dim() != 2 or not self.supported(pcm.size(1)):
+            raise ValueError(f"GruStreamSession: windows of shape {tuple(pcm.shape)} are outside the streaming kernel's range "
+                             f"(see supported()); use the model's forward")
+        if self.std.augment_params[0].enabled:
+            self.std.rand.random()      # the frontend's draw happens on every call, eval mode included: keep the stream's position
+        N, L = pcm.shape
+        if frames is None:      # (it depends on the window's size alone: computed once per size)
+            if L not in self._frames:
+                self._frames[L] = int(self.std.compute_lengths(torch.tensor([L]))[0])
+            frames = self._frames[L]
+        need = ops.gru_stream_workspace_bytes(N, L)
+        if self._ws is None or self._ws.device != pcm.device or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=pcm.device)
+        pair = self.zmuv.pair() if self.zmuv is not None else None
+        prm, buf = self.model._params_struct(), self.model._buffers_struct()
+        return ops.gru_stream_windows(prm, buf, pcm, int(frames), self.std._standard_fb(), self.std.n_mels, pair, self.model.num_labels,
+                                      self._ws, logits=logits)
+
+
 class SimpleGru(RegisteredModel, name="gru"):
     """``SimpleGru`` of the reference (rnn.py:94-130) on the kernels of ``howl_amd/csrc/gru.hip``, the whole model one C-ABI call
     per direction: Conv2d(1,8,3,padding=(1,3)) - BatchNorm - ReLU - MaxPool(1,2) - Conv2d(8,1,3,padding=1) - ReLU - BatchNorm
@@ -636,6 +679,19 @@ class SimpleGru(RegisteredModel, name="gru"):
 
     def forward(self, x, lengths):
         return _GruFunction.apply(self, x, lengths, None, *self.hot_parameters())
+
+    def _params_struct(self):
+        return _lib.HowlGruParams(*[_vp(p) for p in self.hot_parameters()])
+
+    def _buffers_struct(self):
+        e = self.conv_encoder
+        return _lib.HowlGruBuffers(_vp(e[1].running_mean), _vp(e[1].running_var), _vp(e[1].num_batches_tracked), _vp(e[6].running_mean),
+                                   _vp(e[6].running_var), _vp(e[6].num_batches_tracked))
+
+    def stream_session(self, std, zmuv) -> GruStreamSession:
+        """The streaming path for this model behind ``std`` (``StandardAudioTransform``) and ``zmuv`` (``ZmuvTransform`` or None):
+        raw PCM windows -> probabilities in one launch, with scratch of its own (``GruStreamSession``)."""
+        return GruStreamSession(self, std, zmuv)
 
 
 class _LasFunction(torch.autograd.Function):

@@ -396,6 +396,37 @@ def las_stream_windows(state, pcm, frames: int, fbp, n_mels, zmuv_pair, n_labels
     return probs
 
 
+# ---- streaming gru (include/howl_hip_gru_stream.h): one launch from the windows' PCM to their probabilities -------------------------
+
+def gru_stream_supported(n_samples: int, n_mels: int, n_labels: int) -> bool:
+    return bool(_lib.get().cdll.howl_gru_stream_supported(int(n_samples), int(n_mels), int(n_labels)))
+
+
+def gru_stream_workspace_bytes(n_windows: int, n_samples: int) -> int:
+    return int(_lib.get().cdll.howl_gru_stream_workspace_bytes(int(n_windows), int(n_samples)))
+
+
+def gru_stream_windows(prm, buffers, pcm, frames: int, fbp, n_mels, zmuv_pair, n_labels, ws, probs=None, logits=None,
+                       log_eps: float = 1e-7):
+    """(N, L) PCM windows (unit sample stride, any row stride: overlapping views of one clip are fine) -> (N, C) probabilities in one
+    launch; ``prm`` / ``buffers``: ``HowlGruParams`` / ``HowlGruBuffers`` records, read in place; ``frames``: the windows'
+    ``compute_lengths``; ``ws``: uint8 scratch of ``gru_stream_workspace_bytes(N, L)``; ``logits`` (N, C), when given, receives
+    the pre-softmax scores."""
+    if pcm.dim() != 2:
+        raise ValueError("pcm must be (N, L)")
+    if pcm.stride(1) != 1:
+        pcm = pcm.contiguous()
+    if not on_device(pcm) or pcm.dtype != torch.float32:
+        _p(pcm)
+    N, L = pcm.shape
+    if probs is None:
+        probs = torch.empty((N, n_labels), dtype=torch.float32, device=pcm.device)
+    _lib.get().call("howl_gru_stream_windows", ctypes.byref(prm), ctypes.byref(buffers), ctypes.c_void_p(pcm.data_ptr()), pcm.stride(0), N,
+                    L, int(frames), _p(fbp), int(n_mels), log_eps, _p(zmuv_pair, allow_none=True), int(n_labels), _p(probs),
+                    _p(logits, allow_none=True), _p(ws, torch.uint8), ws.numel(), _stream())
+    return probs
+
+
 # ---- streaming seq-lstm / lstm (include/howl_hip_lstm_stream.h): one launch from N PCM chunks to their frame probabilities --------
 
 def lstm_stream_supported(L_max: int, n_mels: int, n_labels: int) -> bool:

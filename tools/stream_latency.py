@@ -9,6 +9,10 @@ is).  Prints one JSON line.  ``--windows`` / ``--repeats`` shorten a run (a prof
 
 ``--model las``: the same protocol for the las model (LasStreamSession), with the launch alone at N = 1 as well.
 
+``--model gru``: the protocol of ``--model las`` for the gru model (GruStreamSession), and the recurrence's time per dependent step:
+for the fused kernel the slope of the launch alone at N = 1 between ``frames = 1`` (2 steps) and ``frames = T`` (22 steps), for
+``gru_fwd4_kernel`` its launch (the library's HIP-event brackets around it, ``howl_profile_read``) over the 22 steps it walks.
+
 ``--model seq-lstm``: the same protocol for ``InferenceEngine.infer`` (LstmStreamSession): (a) 8000-sample chunks (what the live
 client feeds), (b) 16000-sample chunks, both with the state carried from call to call; (c) ``infer_many`` on 64 clips of 1 - 3 s
 against the clip-by-clip ``[reset(); infer(clip)]`` loop (per CALL of 64 clips; ``--windows`` / 20 calls per repeat); and the
@@ -40,7 +44,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--fused-only", action="store_true", help="skip the eager path (a kernel-trace pass over the one launch)")
     ap.add_argument("--eager-only", action="store_true", help="seq-lstm: skip the fused path (a kernel-trace pass over the launch chain)")
-    ap.add_argument("--model", choices=["res8", "las", "seq-lstm", "decide"], default="res8")
+    ap.add_argument("--model", choices=["res8", "las", "gru", "seq-lstm", "decide"], default="res8")
     args = ap.parse_args()
     if args.model == "seq-lstm":
         return main_seq_lstm(args)
@@ -56,9 +60,9 @@ def main():
     from howl_amd.utils.synth import res8_closed_form_state, synthetic_pcm
     dev = torch.device("cuda:0")
     ctx = InferenceContext(["hey", "fire", "fox"], token_type="word", use_blank=False)
-    if args.model == "las":
+    if args.model in ("las", "gru"):
         torch.manual_seed(2024)
-        model = RegisteredModel.find_registered_class("las")(ctx.num_labels).to(dev)
+        model = RegisteredModel.find_registered_class(args.model)(ctx.num_labels).to(dev)
     else:
         model = RegisteredModel.find_registered_class("res8")(ctx.num_labels).to(dev)
         model.load_state_dict(res8_closed_form_state(ctx.num_labels), strict=False)
@@ -92,7 +96,7 @@ def main():
 
     many = []
     session = model.stream_session(std, zmuv)
-    for n in ((1, 64, 256) if args.model == "las" else (64, 256)):
+    for n in ((1, 64, 256) if args.model in ("las", "gru") else (64, 256)):
         stride = (160000 - chunk) // n // 2 * 2
         clip = clips[0, :chunk + (n - 1) * stride].contiguous()
         windows = clip.as_strided((n, chunk), (stride, 1))
@@ -123,6 +127,7 @@ def main():
             row["fused_call_and_host_copy_us_median"] = round(statistics.median(t_f[10:]), 2)
             row["eager_window_probabilities_us_median"] = round(statistics.median(eager_us[10:]), 2)
         many.append(row)
+    per_step = gru_per_step(model, std, zmuv, session, clips[:1, :chunk]) if args.model == "gru" else None
     torch.cuda.synchronize()
     fused_m, eager_m = medians[True], medians[False]
     print(json.dumps({
@@ -131,7 +136,58 @@ def main():
         "windows_per_repeat": args.windows, "warmup_windows": args.warmup,
         "fused_us_medians": [round(v, 2) for v in fused_m], "eager_us_medians": [round(v, 2) for v in eager_m],
         "requirement_max_fused_below_min_eager": (max(fused_m) < min(eager_m)) if eager_m else None,
-        "many_windows": many}), flush=True)
+        "many_windows": many, **({"recurrence_us_per_dependent_step": per_step} if per_step else {})}), flush=True)
+
+
+def gru_per_step(model, std, zmuv, session, window):
+    """One 8000-sample window (T = 41, T1 = 22): the fused launch between two HIP events at 2 and at 22 recurrence steps -> the slope
+    per dependent step; gru_fwd4_kernel between the library's own HIP events over its 22 steps."""
+    import ctypes
+    import torch
+    from howl_amd import lib
+    T = 1 + window.size(1) // 200
+    t1 = (T + 4) // 2
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    launch, queued = {}, {}
+    for frames in (1, T):
+        us = []
+        for i in range(60):
+            e0.record()
+            session.probabilities(window, frames=frames)
+            e1.record()
+            e1.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        launch[min((frames + 4) // 2, t1)] = statistics.median(us[10:])
+        # 200 launches between one pair of events: per launch, the larger of the kernel's time and the host's time to issue it
+        torch.cuda.synchronize()
+        e0.record()
+        for i in range(200):
+            session.probabilities(window, frames=frames)
+        e1.record()
+        e1.synchronize()
+        queued[min((frames + 4) // 2, t1)] = e0.elapsed_time(e1) * 1e3 / 200
+    (s_lo, t_lo), (s_hi, t_hi) = sorted(launch.items())
+    feat = std.log_mel_for_model(window, zmuv)
+    lengths = std.compute_lengths(torch.tensor([window.size(1)]))
+    lb = lib.get()
+    for i in range(10):
+        model(feat, lengths)
+    torch.cuda.synchronize()
+    lb.call("howl_profile_enable", 1)
+    for i in range(50):
+        model(feat, lengths)
+    torch.cuda.synchronize()
+    lb.call("howl_profile_enable", 0)
+    eager = {}
+    tags = ("gru_enc_fwd", "gru_fwd", "gru_head")
+    for i, tag in enumerate(tags):
+        tot, cnt = ctypes.c_double(), ctypes.c_int()
+        lb.call("howl_profile_read", tag.encode(), ctypes.byref(tot), ctypes.byref(cnt), int(i == len(tags) - 1))
+        eager[tag] = round(tot.value * 1e3 / max(cnt.value, 1), 2)
+    return {"fused_launch_us": {f"{k}_steps": round(v, 2) for k, v in launch.items()},
+            "fused_us_per_step": round((t_hi - t_lo) / (s_hi - s_lo), 3),
+            "fused_us_per_launch_200_queued": {f"{k}_steps": round(v, 2) for k, v in queued.items()},
+            "eager_launches_us": eager, "gru_fwd4_steps": t1, "gru_fwd4_us_per_step": round(eager["gru_fwd"] / t1, 3)}
 
 
 def main_seq_lstm(args):
