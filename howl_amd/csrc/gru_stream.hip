@@ -29,6 +29,7 @@
 // written and read back by its own workgroup only, between workgroup barriers.
 #include "howl_logmel.hip.h"
 #include "howl_lstm.hip.h"
+#include "howl_stream.hip.h"
 #include "../../include/howl_hip_gru_stream.h"
 
 namespace {
@@ -305,22 +306,15 @@ GQ_EXPORT int howl_gru_stream_windows(const HowlGruParams* prm, const HowlGruBuf
                                       int frames, const float* fbp, int M, float log_eps, const float* zmuv_pair, int C, float* probs,
                                       float* logits, void* ws, size_t ws_bytes, hipStream_t stream) {
     HOWL_REQUIRE(prm && buffers && pcm && fbp && probs && ws, "howl_gru_stream_windows: null pointer");
-    const float* const* fields = reinterpret_cast<const float* const*>(prm);
-    bool all = true;
-    for (size_t i = 0; i < sizeof(HowlGruParams) / sizeof(const float*); ++i) all = all && fields[i] != nullptr;
-    HOWL_REQUIRE(all, "howl_gru_stream_windows: null pointer in HowlGruParams");
+    HOWL_REQUIRE(stream_record_complete(prm), "howl_gru_stream_windows: null pointer in HowlGruParams");
     HOWL_REQUIRE(buffers->bn1_mean && buffers->bn1_var && buffers->bn2_mean && buffers->bn2_var,
                  "howl_gru_stream_windows: null pointer in HowlGruBuffers");
     HOWL_REQUIRE(gq_supported(L_samples, M, C),
                  "howl_gru_stream_windows: L=%d samples, M=%d, C=%d unsupported (M = 40, %d <= L < %d samples, 1 <= C <= %d: "
                  "howl_gru_stream_supported)", L_samples, M, C, N_FFT, HOP * GQ_MAX_FRAMES, HOWL_GRU_MAX_LABELS);
-    HOWL_REQUIRE(N >= 1 && N <= HOWL_GRU_STREAM_MAX_WINDOWS, "howl_gru_stream_windows: N=%d windows unsupported (1..%d)", N,
-                 HOWL_GRU_STREAM_MAX_WINDOWS);
+    HOWL_STREAM_REQUIRE_GEOMETRY("howl_gru_stream_windows", N, HOWL_GRU_STREAM_MAX_WINDOWS, ld, L_samples);
     const GqGeom gm = gq_geom(L_samples);
     HOWL_REQUIRE(frames >= 1 && frames <= gm.T, "howl_gru_stream_windows: frames=%d outside 1..%d (T = 1 + L / %d)", frames, gm.T, HOP);
-    HOWL_REQUIRE(ld >= 0, "howl_gru_stream_windows: negative window stride %ld", ld);
-    HOWL_REQUIRE((long)(N - 1) * ld + L_samples < (1L << 31), "howl_gru_stream_windows: the windows span %ld samples (32-bit sample offsets)",
-                 (long)(N - 1) * ld + L_samples);
     HOWL_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 3) == 0, "howl_gru_stream_windows: ws must be 4-byte aligned");
     const size_t need = (size_t)N * (size_t)gm.ws_floats * sizeof(float);
     if (ws_bytes < need) {
@@ -328,8 +322,7 @@ GQ_EXPORT int howl_gru_stream_windows(const HowlGruParams* prm, const HowlGruBuf
         return HOWL_E_WORKSPACE;
     }
     const int nsteps = (frames + 4) / 2 < gm.T1 ? (frames + 4) / 2 : gm.T1;
-    // 8-byte sample loads need every window's first sample 8-byte aligned; anything else takes the per-sample path
-    const int aligned = ((N == 1 || (ld & 1) == 0) && (reinterpret_cast<uintptr_t>(pcm) & 7) == 0) ? 1 : 0;
+    const int aligned = stream_pcm_aligned(pcm, ld, N);
     const GqModel model{*prm, buffers->bn1_mean, buffers->bn1_var, buffers->bn2_mean, buffers->bn2_var};
     constexpr size_t lds = (size_t)GQ_LDS_FLOATS * sizeof(float);
     static thread_local size_t granted[16] = {};

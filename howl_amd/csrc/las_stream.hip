@@ -26,6 +26,7 @@
 // between workgroup barriers.
 #include "howl_logmel.hip.h"
 #include "howl_lstm.hip.h"
+#include "howl_stream.hip.h"
 #include "../../include/howl_hip_las_stream.h"
 
 namespace {
@@ -543,10 +544,7 @@ LQ_EXPORT int howl_las_stream_prepare(const HowlLasParams* prm, const HowlLasBuf
     HOWL_REQUIRE(state_bytes >= lq_state_floats(C) * sizeof(float), "howl_las_stream_prepare: state of %zu bytes, C=%d needs %zu",
                  state_bytes, C, lq_state_floats(C) * sizeof(float));
     HOWL_REQUIRE((reinterpret_cast<uintptr_t>(state) & 15) == 0, "howl_las_stream_prepare: state must be 16-byte aligned");
-    const float* const* fields = reinterpret_cast<const float* const*>(prm);
-    bool all = true;
-    for (size_t i = 0; i < sizeof(HowlLasParams) / sizeof(const float*); ++i) all = all && fields[i] != nullptr;
-    HOWL_REQUIRE(all, "howl_las_stream_prepare: null pointer in HowlLasParams");
+    HOWL_REQUIRE(stream_record_complete(prm), "howl_las_stream_prepare: null pointer in HowlLasParams");
     HOWL_REQUIRE(buffers->bn1_mean && buffers->bn1_var && buffers->bn2_mean && buffers->bn2_var,
                  "howl_las_stream_prepare: null pointer in HowlLasBuffers");
     const LqPrep a{*prm, buffers->bn1_mean, buffers->bn1_var, buffers->bn2_mean, buffers->bn2_var};
@@ -563,13 +561,9 @@ LQ_EXPORT int howl_las_stream_windows(const void* state, const float* pcm, long 
     HOWL_REQUIRE(lq_supported(L_samples, M, C),
                  "howl_las_stream_windows: L=%d samples, M=%d, C=%d unsupported (M = 40, %d <= L < %d samples, 1 <= C <= %d: "
                  "howl_las_stream_supported)", L_samples, M, C, N_FFT, HOP * LQ_MAX_FRAMES, HOWL_LAS_MAX_LABELS);
-    HOWL_REQUIRE(N >= 1 && N <= HOWL_LAS_STREAM_MAX_WINDOWS, "howl_las_stream_windows: N=%d windows unsupported (1..%d)", N,
-                 HOWL_LAS_STREAM_MAX_WINDOWS);
+    HOWL_STREAM_REQUIRE_GEOMETRY("howl_las_stream_windows", N, HOWL_LAS_STREAM_MAX_WINDOWS, ld, L_samples);
     const LqGeom gm = lq_geom(L_samples);
     HOWL_REQUIRE(frames >= 1 && frames <= gm.T, "howl_las_stream_windows: frames=%d outside 1..%d (T = 1 + L / %d)", frames, gm.T, HOP);
-    HOWL_REQUIRE(ld >= 0, "howl_las_stream_windows: negative window stride %ld", ld);
-    HOWL_REQUIRE((long)(N - 1) * ld + L_samples < (1L << 31), "howl_las_stream_windows: the windows span %ld samples (32-bit sample offsets)",
-                 (long)(N - 1) * ld + L_samples);
     HOWL_REQUIRE((reinterpret_cast<uintptr_t>(state) & 15) == 0 && (reinterpret_cast<uintptr_t>(ws) & 3) == 0,
                  "howl_las_stream_windows: state must be 16-byte aligned and ws 4-byte aligned");
     const size_t need = (size_t)N * (size_t)gm.ws_floats * sizeof(float);
@@ -578,8 +572,7 @@ LQ_EXPORT int howl_las_stream_windows(const void* state, const float* pcm, long 
         return HOWL_E_WORKSPACE;
     }
     const int nsteps = (((frames + 2) / 2) + 2) / 2;      // <= T2, as frames <= T
-    // 8-byte sample loads need every window's first sample 8-byte aligned; anything else takes the per-sample path
-    const int aligned = ((N == 1 || (ld & 1) == 0) && (reinterpret_cast<uintptr_t>(pcm) & 7) == 0) ? 1 : 0;
+    const int aligned = stream_pcm_aligned(pcm, ld, N);
     constexpr size_t lds = (size_t)LQ_LDS_FLOATS * sizeof(float);
     static thread_local size_t granted[16] = {};
     howl_raise_lds(reinterpret_cast<const void*>(las_stream_kernel), lds, granted, "howl_las_stream_windows");

@@ -22,6 +22,7 @@
 //   up to 83 frames (27 rows; 1 s): 4 waves (the frontend's transpose tiles are per wave: 37,376 B), <= 6 tiles per wave
 //     static 60,672 B + dynamic <= 83 KB
 #include "howl_logmel.hip.h"
+#include "howl_stream.hip.h"
 #include "../../include/howl_hip_stream.h"
 
 namespace {
@@ -403,14 +404,9 @@ int howl_res8_stream_windows(const void* state, const float* pcm, long ld, int N
     HOWL_REQUIRE(sr_supported(L_samples, M, C),
                  "howl_res8_stream_windows: L=%d samples, M=%d, C=%d unsupported (M = 40, 3..%d frames, C <= %d: howl_res8_stream_supported)",
                  L_samples, M, C, SR_MAX_FRAMES, HOWL_STREAM_MAX_CLASSES);
-    HOWL_REQUIRE(N >= 1 && N <= HOWL_STREAM_MAX_WINDOWS, "howl_res8_stream_windows: N=%d windows unsupported (1..%d)", N,
-                 HOWL_STREAM_MAX_WINDOWS);
-    HOWL_REQUIRE(ld >= 0, "howl_res8_stream_windows: negative window stride %ld", ld);
-    HOWL_REQUIRE((long)(N - 1) * ld + L_samples < (1L << 31), "howl_res8_stream_windows: the windows span %ld samples (32-bit sample offsets)",
-                 (long)(N - 1) * ld + L_samples);
+    HOWL_STREAM_REQUIRE_GEOMETRY("howl_res8_stream_windows", N, HOWL_STREAM_MAX_WINDOWS, ld, L_samples);
     const SrPlan p = sr_plan(L_samples);
-    // 8-byte sample loads need every window's first sample 8-byte aligned; anything else takes the per-sample path
-    const int aligned = ((N == 1 || (ld & 1) == 0) && (reinterpret_cast<uintptr_t>(pcm) & 7) == 0) ? 1 : 0;
+    const int aligned = stream_pcm_aligned(pcm, ld, N);
     if (p.small)
         sr_launch<8, 2>(p, N, stream, static_cast<const float*>(state), pcm, ld, L_samples, fbp, log_eps, zmuv_pair, aligned, C, probs, logits);
     else

@@ -18,6 +18,7 @@ from howl_amd import ops, parallel
 from howl_amd.settings import _EnvSettings
 
 from .base import RegisteredModel
+from .stream import PreparedStreamSession
 
 __all__ = ["Res8", "Res8Settings", "Res8StreamSession", "MobileNetClassifier", "CnnSettings", "SmallCnn", "SequentialCnn"]
 
@@ -98,54 +99,32 @@ class _Res8Function(torch.autograd.Function):
         return (None, None) + tuple(grads)
 
 
-class Res8StreamSession:
+class Res8StreamSession(PreparedStreamSession):
     """Streaming res8: ``probabilities(pcm)`` takes (N, L) raw PCM windows to their (N, C) class probabilities in ONE kernel launch
     (``howl_res8_stream_windows``: log-mel + ZMUV, conv0, the six 3x3 layers, mean, Linear and softmax, one workgroup per window).
     The session owns its prepared state (packed weights, folded BatchNorm running statistics), so two engines on two streams share
     nothing; it is prepared again whenever a hot parameter or a running buffer of the model was replaced or written through torch
     since the last launch (``data_ptr()`` / ``_version``: ``load_state_dict``, an optimiser step).  Writes that torch does not see
-    (the fused trainer's in-kernel AdamW) need ``refresh()``.  Eval mode only, standard filterbank only."""
-
-    def __init__(self, model, std, zmuv):
-        self.model, self.std, self.zmuv = model, std, zmuv
-        self._state = None
-        self._key = None
-
-    def supported(self, n_samples: int) -> bool:
-        """Windows of ``n_samples`` samples are inside the kernel's range (40 mel bins, 3..83 frames, <= 64 labels) and the frontend
-        would not draw a VTLP filterbank for them."""
-        vtlp = self.std.augment_params[0].enabled and self.std.training
-        return not vtlp and ops.res8_stream_supported(n_samples, self.std.n_mels, self.model.num_labels)
-
-    def refresh(self):
-        """Forces the next call to prepare the state again."""
-        self._key = None
+    (the fused trainer's in-kernel AdamW) need ``refresh()``.  Eval mode only, standard filterbank only.  The kernel's range, which
+    ``supported()`` answers for: 40 mel bins, 3..83 frames, <= 64 labels."""
+    RUNS = "eval-mode BatchNorm (running statistics)"
+    in_range = staticmethod(ops.res8_stream_supported)
 
     def _watched(self):
         bns = [getattr(self.model, f"bn{i}") for i in range(1, 7)]
         return self.model.hot_parameters() + [b.running_mean for b in bns] + [b.running_var for b in bns]
 
-    def _prepared_state(self, device):
-        key = tuple((t.data_ptr(), t._version) for t in self._watched())
-        if self._state is None or self._state.device != device or key != self._key:
-            if self._state is None or self._state.device != device:
-                self._state = torch.empty(ops.res8_stream_state_bytes(self.model.num_labels), dtype=torch.uint8, device=device)
-            ops.res8_stream_prepare(self.model._params_struct(), self.model.num_labels, self._state)
-            self._key = key
-        return self._state
+    def _state_bytes(self):
+        return ops.res8_stream_state_bytes(self.model.num_labels)
+
+    def _prepare(self, state):
+        ops.res8_stream_prepare(self.model._params_struct(), self.model.num_labels, state)
 
     @torch.no_grad()
     def probabilities(self, pcm: torch.Tensor, logits: torch.Tensor = None) -> torch.Tensor:
         """pcm: (N, L) fp32 on the device, unit sample stride (rows may be overlapping views of one clip) -> (N, C) on the device."""
-        if self.model.training:
-            raise RuntimeError("Res8StreamSession runs eval-mode BatchNorm (running statistics): call model.eval() first")
-        if pcm.dim() != 2 or not self.supported(pcm.size(1)):
-            raise ValueError(f"Res8StreamSession: windows of shape {tuple(pcm.shape)} are outside the streaming kernel's range "
-                             f"(see supported()); use the model's forward")
-        if self.std.augment_params[0].enabled:
-            self.std.rand.random()      # the frontend's draw happens on every call, eval mode included: keep the stream's position
-        state = self._prepared_state(pcm.device)
-        pair = self.zmuv.pair() if self.zmuv is not None else None
+        self._enter(pcm)
+        state, pair = self._prepared_state(pcm.device), self._pair()
         return ops.res8_stream_windows(state, pcm, self.std._standard_fb(), self.std.n_mels, pair, self.model.num_labels, logits=logits)
 
 

@@ -63,7 +63,7 @@ class InferenceEngine:
         self.label_history = []
         # infer as ONE launch (LstmStreamSession) instead of the frontend + LSTM + head + softmax chain: off unless asked for
         self.fused_chunks = os.environ.get("HOWL_STREAM_FUSED") == "1"
-        self._chunk_session = None
+        self._stream_session = None      # (see _session)
         # infer_many: the frame-by-frame decision logic of all clips as ONE launch behind the probabilities (DeviceDecider) instead
         # of the host loops: off unless asked for
         self.device_decisions = os.environ.get("HOWL_DECIDE_DEVICE") == "1"
@@ -114,15 +114,20 @@ class InferenceEngine:
         prediction = (prediction * self.inference_weights).astype(prediction.dtype, copy=False)
         return prediction / prediction.sum()
 
-    def _lstm_session(self, kind, n_samples: int):
-        """The streaming session for chunks of up to ``n_samples`` samples, or None when it does not apply (another model, training
-        mode, a length outside the kernel's range): the caller then takes the launch chain."""
-        if not isinstance(self.model, kind) or self.model.training:
+    def _session(self, kinds, n_samples: int):
+        """The engine's streaming session for rows of up to ``n_samples`` samples, or None when it does not apply (the model is none
+        of ``kinds``, training mode, a length outside the kernel's range): the caller then takes the launch chain.  The session is
+        the engine's own, made on first use and again when the model or a transform was replaced."""
+        if not isinstance(self.model, kinds) or self.model.training:
             return None
-        s = self._chunk_session
+        s = self._stream_session
         if s is None or s.model is not self.model or s.std is not self.std or s.zmuv is not self.zmuv:
-            s = self._chunk_session = self.model.stream_session(self.std, self.zmuv)
+            s = self._stream_session = self.model.stream_session(self.std, self.zmuv)
         return s if s.supported(n_samples) else None
+
+    def _lstm_session(self, kind, n_samples: int):
+        """``LstmStreamSession`` for chunks of up to ``n_samples`` samples where the model is a ``kind`` (see ``_session``)."""
+        return self._session(kind, n_samples)
 
     def _device_decider(self, mode: int, t_max: int, min_delta_ms: float, n_clips: int):
         """The decision launch for clips of up to ``t_max`` frames with the settings as they are now, or None when the switch is off
@@ -221,7 +226,6 @@ class FrameInferenceEngine(InferenceEngine):
         # ingest_frame as ONE launch (Res8StreamSession, LasStreamSession, GruStreamSession) instead of the frontend + model +
         # softmax chain: off unless asked for
         self.fused_windows = os.environ.get("HOWL_STREAM_FUSED") == "1"
-        self._stream_session = None
         self._frames_cache = {}
 
     def _stateless(self) -> bool:
@@ -360,15 +364,7 @@ class FrameInferenceEngine(InferenceEngine):
     def infer(self, audio_data: torch.Tensor) -> bool:
         if not self._stateless():
             return self._infer_sequential(audio_data)
-        probs = self.window_probabilities(audio_data)
-        sequence_present = False
-        for prediction in probs:
-            self._append_probability_frame(self._weighted(prediction), curr_time=self.curr_time)
-            self.curr_time += self.eval_stride_size_ms
-            if self.sequence_present(self.curr_time):
-                sequence_present = True
-                break
-        return sequence_present
+        return self._run_fsm(self.window_probabilities(audio_data))
 
     def _infer_sequential(self, audio_data: torch.Tensor) -> bool:
         sequence_present = False
@@ -396,29 +392,22 @@ class FrameInferenceEngine(InferenceEngine):
         the kernel's range): ``ingest_frame`` then takes the launch chain."""
         if frame.dim() != 1 or frame.dtype != torch.float32:
             return None
-        if isinstance(self.model, SimpleLstm):      # (a window with no whole 512-sample frame has compute_lengths < 1: the chain's business)
-            return self._lstm_session(SimpleLstm, frame.size(-1)) if self._window_frames(frame) is not None else None
-        if not isinstance(self.model, (Res8, LASClassifier, SimpleGru)) or self.model.training:
-            return None
-        s = self._stream_session
-        if s is None or s.model is not self.model or s.std is not self.std or s.zmuv is not self.zmuv:
-            s = self._stream_session = self.model.stream_session(self.std, self.zmuv)
-        return s if s.supported(frame.size(-1)) else None
+        if isinstance(self.model, SimpleLstm) and self._window_frames(frame) is None:
+            return None      # (a window with no whole 512-sample frame has compute_lengths < 1: the chain's business)
+        return self._session((Res8, LASClassifier, SimpleGru, SimpleLstm), frame.size(-1))
 
     @torch.no_grad()
     def ingest_frame(self, frame: torch.Tensor, curr_time: float = None) -> int:
         """One window, as the live client feeds it (``inference.py:247-267``)."""
         self.std = self.std.to(frame.device)
         session = self._fused_session(frame) if self.fused_windows else None
-        if session is not None and isinstance(self.model, SimpleLstm):      # one launch, one host copy; frames as compute_lengths
-            frames = self._window_frames(frame)
-            prediction = session.probabilities(frame.reshape(1, -1), frames=frames)[0][0].cpu().numpy()
-            return self._append_probability_frame(self._weighted(prediction), curr_time=curr_time)
-        if session is not None:      # one launch, one host copy
-            prediction = session.probabilities(frame.reshape(1, -1))[0].cpu().numpy()
-            return self._append_probability_frame(self._weighted(prediction), curr_time=curr_time)
-        lengths = torch.tensor([frame.size(-1)]).to(frame.device)
-        transformed_lengths = self.std.compute_lengths(lengths)
-        transformed_frame = self.std.log_mel_for_model(frame.unsqueeze(0), self.zmuv, channels=getattr(self.model, "FEATURE_CHANNELS", 1))
-        prediction = self.model(transformed_frame, transformed_lengths).softmax(-1)[0].cpu().numpy()
-        return self._append_probability_frame(self._weighted(prediction), curr_time=curr_time)
+        if session is None:
+            lengths = torch.tensor([frame.size(-1)]).to(frame.device)
+            transformed_lengths = self.std.compute_lengths(lengths)
+            transformed_frame = self.std.log_mel_for_model(frame.unsqueeze(0), self.zmuv, channels=getattr(self.model, "FEATURE_CHANNELS", 1))
+            prediction = self.model(transformed_frame, transformed_lengths).softmax(-1)[0]
+        elif isinstance(self.model, SimpleLstm):      # one launch, one host copy; frames as compute_lengths
+            prediction = session.probabilities(frame.reshape(1, -1), frames=self._window_frames(frame))[0][0]
+        else:      # one launch, one host copy
+            prediction = session.probabilities(frame.reshape(1, -1))[0]
+        return self._append_probability_frame(self._weighted(prediction.cpu().numpy()), curr_time=curr_time)

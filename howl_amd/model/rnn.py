@@ -19,6 +19,7 @@ from howl_amd import ops, parallel
 from howl_amd.settings import _EnvSettings
 
 from .base import RegisteredModel
+from .stream import PreparedStreamSession, StreamSession
 
 __all__ = ["FixedAttentionModuleConfig", "GruStreamSession", "LASClassifier", "LASClassifierConfig", "LASEncoderConfig",
            "LasStreamSession", "LstmConfig", "LstmStreamSession", "SequentialLstm", "SimpleGru", "SimpleLstm"]
@@ -268,26 +269,24 @@ class _HeadFunction(torch.autograd.Function):
         return (dx,) + tuple(grads)
 
 
-class LstmStreamSession:
+class LstmStreamSession(StreamSession):
     """Streaming seq-lstm / lstm: ``probabilities(pcm, ...)`` takes N independent raw PCM chunks to their class probabilities in ONE
     kernel launch (``howl_lstm_stream_chunks``: log-mel + ZMUV, the recurrence, the head and the softmax, four streams per
     workgroup; no gate / cell / hidden-sequence stores, nothing of the head through HBM).  The weights are read in place on every
-    call: nothing is prepared, nothing can go stale.  Eval mode only, standard filterbank only.
+    call: nothing is prepared, nothing can go stale.  Eval mode only, standard filterbank only.  The kernel's range, which
+    ``supported()`` answers for chunks of UP TO ``n_samples`` samples: 40 mel bins, 400 samples .. 8192 frames, <= 64 labels.
 
     ``seq-lstm``: probs (N, 1 + L_max // 200, C), rows behind a stream's last frame zero, and the carried state as the pair of
     (1, N, 128) tensors ``model.streaming_state`` holds.  ``lstm``: the head on the final hidden state only, probs (N, C), no state
     (``SimpleLstm`` is stateless between calls, rnn.py:89-90)."""
+    RUNS = "the inference path (no saved activations)"
+    UNIT = "chunks"
+    in_range = staticmethod(ops.lstm_stream_supported)
 
     def __init__(self, model, std, zmuv):
-        self.model, self.std, self.zmuv = model, std, zmuv
+        super().__init__(model, std, zmuv)
         self.last_only = isinstance(model, SimpleLstm)
         self._own = None      # the state pair this session returned last: handed back, it is advanced in place
-
-    def supported(self, n_samples: int) -> bool:
-        """Chunks of up to ``n_samples`` samples are inside the kernel's range (40 mel bins, 400 samples .. 8192 frames, <= 64 labels)
-        and the frontend would not draw a VTLP filterbank for them."""
-        vtlp = self.std.augment_params[0].enabled and self.std.training
-        return not vtlp and ops.lstm_stream_supported(n_samples, self.std.n_mels, self.model.num_labels)
 
     @torch.no_grad()
     def probabilities(self, pcm: torch.Tensor, n_samples: torch.Tensor = None, frames: torch.Tensor = None, state=None,
@@ -297,13 +296,7 @@ class LstmStreamSession:
         the (h, c) pair to start from, (1, N, 128) each, None = zeros.  -> (probs, state).  The returned state tensors belong to the
         session: handed back as ``state`` of the next call they are advanced in place (no copy); any other pair is copied first.
         ``return_state=False`` with ``state=None``: no state is carried at all (a pass over whole clips)."""
-        if self.model.training:
-            raise RuntimeError("LstmStreamSession runs the inference path (no saved activations): call model.eval() first")
-        if pcm.dim() != 2 or not self.supported(pcm.size(1)):
-            raise ValueError(f"LstmStreamSession: chunks of shape {tuple(pcm.shape)} are outside the streaming kernel's range "
-                             f"(see supported()); use the model's forward")
-        if self.std.augment_params[0].enabled:
-            self.std.rand.random()      # the frontend's draw happens on every call, eval mode included: keep the stream's position
+        self._enter(pcm)
         N = pcm.size(0)
         h = c = None
         if not self.last_only and (state is not None or return_state):
@@ -321,7 +314,7 @@ class LstmStreamSession:
         l, d = self.model.lstm, self.model.dnn
         lstm_prm = _lib.HowlLstmParams(_vp(l.weight_ih_l0), _vp(l.weight_hh_l0), _vp(l.bias_ih_l0), _vp(l.bias_hh_l0))
         head_prm = _lib.HowlHeadParams(_vp(d[0].weight), _vp(d[0].bias), _vp(d[2].weight), _vp(d[2].bias))
-        pair = self.zmuv.pair() if self.zmuv is not None else None
+        pair = self._pair()
         probs = ops.lstm_stream_chunks(lstm_prm, head_prm, pcm, self.std._standard_fb(), self.std.n_mels, pair, self.model.num_labels,
                                        n_samples=n_samples, frames=frames, h=h, c=c, last_only=self.last_only, logits=logits)
         self._own = (h, c) if h is not None else None
@@ -513,47 +506,29 @@ class _GruFunction(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads)
 
 
-class GruStreamSession:
+class GruStreamSession(StreamSession):
     """Streaming gru: ``probabilities(pcm)`` takes (N, L) raw PCM windows to their (N, C) class probabilities in ONE kernel launch
     (``howl_gru_stream_windows``: log-mel and ZMUV, both convolutions, the recurrence, the head and the softmax, one workgroup per
     window).  The kernel reads the model's parameters and running statistics in place, so there is no prepared state and nothing
     to refresh: a ``load_state_dict``, an optimiser step or a write torch does not see is in the next call's answer.  The session
-    owns its scratch, so two engines on two streams share nothing.  Eval mode only, standard filterbank only."""
-
-    def __init__(self, model, std, zmuv):
-        self.model, self.std, self.zmuv = model, std, zmuv
-        self._ws = None
-        self._frames = {}
-
-    def supported(self, n_samples: int) -> bool:
-        """Windows of ``n_samples`` samples are inside the kernel's range (40 mel bins, 512 samples .. 83 frames, <= 64 labels) and
-        the frontend would not draw a VTLP filterbank for them."""
-        vtlp = self.std.augment_params[0].enabled and self.std.training
-        return not vtlp and ops.gru_stream_supported(n_samples, self.std.n_mels, self.model.num_labels)
+    owns its scratch, so two engines on two streams share nothing.  Eval mode only, standard filterbank only.  The kernel's range,
+    which ``supported()`` answers for: 40 mel bins, 512 samples .. 83 frames, <= 64 labels."""
+    RUNS = "eval-mode BatchNorm (running statistics) and no dropout"
+    in_range = staticmethod(ops.gru_stream_supported)
 
     @torch.no_grad()
     def probabilities(self, pcm: torch.Tensor, frames: int = None, logits: torch.Tensor = None) -> torch.Tensor:
         """pcm: (N, L) fp32 on the device, unit sample stride (rows may be overlapping views of one clip); ``frames``: the frames the
         recurrence runs over (None: ``std.compute_lengths(L)``) -> (N, C) on the device."""
-        if self.model.training:
-            raise RuntimeError("GruStreamSession runs eval-mode BatchNorm (running statistics) and no dropout: call model.eval() first")
-        if pcm.dim() != 2 or not self.supported(pcm.size(1)):
-            raise ValueError(f"GruStreamSession: windows of shape {tuple(pcm.shape)} are outside the streaming kernel's range "
-                             f"(see supported()); use the model's forward")
-        if self.std.augment_params[0].enabled:
-            self.std.rand.random()      # the frontend's draw happens on every call, eval mode included: keep the stream's position
+        self._enter(pcm)
         N, L = pcm.shape
-        if frames is None:      # (it depends on the window's size alone: computed once per size)
-            if L not in self._frames:
-                self._frames[L] = int(self.std.compute_lengths(torch.tensor([L]))[0])
-            frames = self._frames[L]
-        need = ops.gru_stream_workspace_bytes(N, L)
-        if self._ws is None or self._ws.device != pcm.device or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=pcm.device)
-        pair = self.zmuv.pair() if self.zmuv is not None else None
+        if frames is None:
+            frames = self._frames_of(L)
+        ws = self._workspace(ops.gru_stream_workspace_bytes(N, L), pcm.device)
+        pair = self._pair()
         prm, buf = self.model._params_struct(), self.model._buffers_struct()
         return ops.gru_stream_windows(prm, buf, pcm, int(frames), self.std._standard_fb(), self.std.n_mels, pair, self.model.num_labels,
-                                      self._ws, logits=logits)
+                                      ws, logits=logits)
 
 
 class SimpleGru(RegisteredModel, name="gru"):
@@ -710,7 +685,7 @@ class _LasFunction(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads)
 
 
-class LasStreamSession:
+class LasStreamSession(PreparedStreamSession):
     """Streaming las: ``probabilities(pcm)`` takes (N, L) raw PCM windows to their (N, C) class probabilities in ONE kernel launch
     (``howl_las_stream_windows``: log-mel, deltas and ZMUV, both convolutions, the input projections, both recurrences, the
     attention, the head and the softmax, one workgroup per window).  The session owns its prepared state (W_ih and the V / K
@@ -718,62 +693,34 @@ class LasStreamSession:
     two engines on two streams share nothing; the state is prepared again whenever a hot parameter, a BatchNorm weight or bias or
     a running buffer of the model was replaced or written through torch since the last launch (``data_ptr()`` / ``_version``:
     ``load_state_dict``, an optimiser step).  Writes that torch does not see need ``refresh()``.  Eval mode only, standard
-    filterbank only."""
-
-    def __init__(self, model, std, zmuv):
-        self.model, self.std, self.zmuv = model, std, zmuv
-        self._state = None
-        self._key = None
-        self._ws = None
-        self._frames = {}
-
-    def supported(self, n_samples: int) -> bool:
-        """Windows of ``n_samples`` samples are inside the kernel's range (40 mel bins, 512 samples .. 83 frames, <= 64 labels) and
-        the frontend would not draw a VTLP filterbank for them."""
-        vtlp = self.std.augment_params[0].enabled and self.std.training
-        return not vtlp and ops.las_stream_supported(n_samples, self.std.n_mels, self.model.num_labels)
-
-    def refresh(self):
-        """Forces the next call to prepare the state again."""
-        self._key = None
+    filterbank only.  The kernel's range, which ``supported()`` answers for: 40 mel bins, 512 samples .. 83 frames, <= 64 labels."""
+    RUNS = "eval-mode BatchNorm (running statistics) and no dropout"
+    in_range = staticmethod(ops.las_stream_supported)
 
     def _watched(self):
         bn1, bn2 = self.model.encoder.conv_encoder[1], self.model.encoder.conv_encoder[5]
         return self.model.hot_parameters() + [bn1.running_mean, bn1.running_var, bn2.running_mean, bn2.running_var]
 
-    def _prepared_state(self, device):
-        key = tuple((t.data_ptr(), t._version) for t in self._watched())
-        if self._state is None or self._state.device != device or key != self._key:
-            if self._state is None or self._state.device != device:
-                self._state = torch.empty(ops.las_stream_state_bytes(self.model.num_labels), dtype=torch.uint8, device=device)
-            prm = _lib.HowlLasParams(*[_vp(p) for p in self.model.hot_parameters()])
-            ops.las_stream_prepare(prm, self.model._bn_buffers(), self.model.num_labels, self._state)
-            self._key = key
-        return self._state
+    def _state_bytes(self):
+        return ops.las_stream_state_bytes(self.model.num_labels)
+
+    def _prepare(self, state):
+        prm = _lib.HowlLasParams(*[_vp(p) for p in self.model.hot_parameters()])
+        ops.las_stream_prepare(prm, self.model._bn_buffers(), self.model.num_labels, state)
 
     @torch.no_grad()
     def probabilities(self, pcm: torch.Tensor, frames: int = None, logits: torch.Tensor = None) -> torch.Tensor:
         """pcm: (N, L) fp32 on the device, unit sample stride (rows may be overlapping views of one clip); ``frames``: the frames the
         recurrences and the attention run over (None: ``std.compute_lengths(L)``) -> (N, C) on the device."""
-        if self.model.training:
-            raise RuntimeError("LasStreamSession runs eval-mode BatchNorm (running statistics) and no dropout: call model.eval() first")
-        if pcm.dim() != 2 or not self.supported(pcm.size(1)):
-            raise ValueError(f"LasStreamSession: windows of shape {tuple(pcm.shape)} are outside the streaming kernel's range "
-                             f"(see supported()); use the model's forward")
-        if self.std.augment_params[0].enabled:
-            self.std.rand.random()      # the frontend's draw happens on every call, eval mode included: keep the stream's position
+        self._enter(pcm)
         N, L = pcm.shape
-        if frames is None:      # (it depends on the window's size alone: computed once per size)
-            if L not in self._frames:
-                self._frames[L] = int(self.std.compute_lengths(torch.tensor([L]))[0])
-            frames = self._frames[L]
+        if frames is None:
+            frames = self._frames_of(L)
         state = self._prepared_state(pcm.device)
-        need = ops.las_stream_workspace_bytes(N, L)
-        if self._ws is None or self._ws.device != pcm.device or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=pcm.device)
-        pair = self.zmuv.pair() if self.zmuv is not None else None
+        ws = self._workspace(ops.las_stream_workspace_bytes(N, L), pcm.device)
+        pair = self._pair()
         return ops.las_stream_windows(state, pcm, int(frames), self.std._standard_fb(), self.std.n_mels, pair, self.model.num_labels,
-                                      self._ws, logits=logits)
+                                      ws, logits=logits)
 
 
 class _LasEncoder(nn.Module):

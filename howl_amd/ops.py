@@ -322,14 +322,18 @@ def adamw_step(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=1.0):
                     weight_decay, step, grad_scale, _stream())
 
 
+def _stream_query(symbol, result):
+    """The streaming entry points' queries are one wrapper for every model: ``*_stream_supported(n_samples, n_mels, n_labels) -> bool``,
+    ``*_stream_state_bytes(n_labels) -> int``, ``*_stream_workspace_bytes(n_windows, n_samples) -> int``."""
+    def query(*values):
+        return result(getattr(_lib.get().cdll, symbol)(*[int(v) for v in values]))
+    return query
+
+
 # ---- streaming res8 (include/howl_hip_stream.h): one launch from the windows' PCM to their probabilities ----------------------------
 
-def res8_stream_supported(n_samples: int, n_mels: int, n_labels: int) -> bool:
-    return bool(_lib.get().cdll.howl_res8_stream_supported(int(n_samples), int(n_mels), int(n_labels)))
-
-
-def res8_stream_state_bytes(n_labels: int) -> int:
-    return int(_lib.get().cdll.howl_res8_stream_state_bytes(int(n_labels)))
+res8_stream_supported = _stream_query("howl_res8_stream_supported", bool)
+res8_stream_state_bytes = _stream_query("howl_res8_stream_state_bytes", int)
 
 
 def res8_stream_prepare(prm, n_labels: int, state: torch.Tensor) -> torch.Tensor:
@@ -358,16 +362,9 @@ def res8_stream_windows(state, pcm, fbp, n_mels, zmuv_pair, n_labels, probs=None
 
 # ---- streaming las (include/howl_hip_las_stream.h): one launch from the windows' PCM to their probabilities -------------------------
 
-def las_stream_supported(n_samples: int, n_mels: int, n_labels: int) -> bool:
-    return bool(_lib.get().cdll.howl_las_stream_supported(int(n_samples), int(n_mels), int(n_labels)))
-
-
-def las_stream_state_bytes(n_labels: int) -> int:
-    return int(_lib.get().cdll.howl_las_stream_state_bytes(int(n_labels)))
-
-
-def las_stream_workspace_bytes(n_windows: int, n_samples: int) -> int:
-    return int(_lib.get().cdll.howl_las_stream_workspace_bytes(int(n_windows), int(n_samples)))
+las_stream_supported = _stream_query("howl_las_stream_supported", bool)
+las_stream_state_bytes = _stream_query("howl_las_stream_state_bytes", int)
+las_stream_workspace_bytes = _stream_query("howl_las_stream_workspace_bytes", int)
 
 
 def las_stream_prepare(prm, buffers, n_labels: int, state: torch.Tensor) -> torch.Tensor:
@@ -398,12 +395,8 @@ def las_stream_windows(state, pcm, frames: int, fbp, n_mels, zmuv_pair, n_labels
 
 # ---- streaming gru (include/howl_hip_gru_stream.h): one launch from the windows' PCM to their probabilities -------------------------
 
-def gru_stream_supported(n_samples: int, n_mels: int, n_labels: int) -> bool:
-    return bool(_lib.get().cdll.howl_gru_stream_supported(int(n_samples), int(n_mels), int(n_labels)))
-
-
-def gru_stream_workspace_bytes(n_windows: int, n_samples: int) -> int:
-    return int(_lib.get().cdll.howl_gru_stream_workspace_bytes(int(n_windows), int(n_samples)))
+gru_stream_supported = _stream_query("howl_gru_stream_supported", bool)
+gru_stream_workspace_bytes = _stream_query("howl_gru_stream_workspace_bytes", int)
 
 
 def gru_stream_windows(prm, buffers, pcm, frames: int, fbp, n_mels, zmuv_pair, n_labels, ws, probs=None, logits=None,
@@ -429,8 +422,7 @@ def gru_stream_windows(prm, buffers, pcm, frames: int, fbp, n_mels, zmuv_pair, n
 
 # ---- streaming seq-lstm / lstm (include/howl_hip_lstm_stream.h): one launch from N PCM chunks to their frame probabilities --------
 
-def lstm_stream_supported(L_max: int, n_mels: int, n_labels: int) -> bool:
-    return bool(_lib.get().cdll.howl_lstm_stream_supported(int(L_max), int(n_mels), int(n_labels)))
+lstm_stream_supported = _stream_query("howl_lstm_stream_supported", bool)
 
 
 def lstm_stream_chunks(lstm_prm, head_prm, pcm, fbp, n_mels, zmuv_pair, n_labels, n_samples=None, frames=None, h=None, c=None,

@@ -37,6 +37,57 @@ if str(ROOT) not in sys.path:
 os.environ.setdefault("NUM_MELS", "40")
 
 
+def setup(model_name, use_blank):
+    """-> (context, model, std, zmuv, clips) on cuda:0: the three-word context, the eval-mode model (res8 with its closed-form state,
+    the others from seed 2024), the frontend, and the ZMUV statistics of the first second of the 8 synthetic clips of 10 s."""
+    import torch
+    from howl_amd.context import InferenceContext
+    from howl_amd.data.transform.operator import ZmuvTransform
+    from howl_amd.data.transform.transform import StandardAudioTransform
+    from howl_amd.model import RegisteredModel
+    from howl_amd.utils.synth import res8_closed_form_state, synthetic_pcm
+    dev = torch.device("cuda:0")
+    ctx = InferenceContext(["hey", "fire", "fox"], token_type="word", use_blank=use_blank)
+    if model_name != "res8":
+        torch.manual_seed(2024)
+    model = RegisteredModel.find_registered_class(model_name)(ctx.num_labels).to(dev)
+    if model_name == "res8":
+        model.load_state_dict(res8_closed_form_state(ctx.num_labels), strict=False)
+    model.eval()
+    std = StandardAudioTransform().to(dev).eval()
+    zmuv = ZmuvTransform().to(dev)
+    clips = synthetic_pcm(8, 160000, seed=77).to(dev)
+    zmuv.update(std(clips[:1, :16000]))
+    return ctx, model, std, zmuv, clips
+
+
+def launch_us(fn):
+    """``fn()`` 60 times, each between two HIP events: the median of the last 50, us."""
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    us = []
+    for _ in range(60):
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        us.append(e0.elapsed_time(e1) * 1e3)
+    return statistics.median(us[10:])
+
+
+def alternate(paths, run, warm, calls, repeats):
+    """``run(path, n, first)`` -> the wall times of ``n`` calls on ``path``, starting at item ``first`` of whatever it walks.  ``warm``
+    calls of warm-up per path, then ``repeats`` repeats of ``calls`` calls, the paths alternating repeat by repeat
+    -> {path: [the median of each repeat, us]} for the paths True and False (one that is not in ``paths``: [])."""
+    for path in paths:
+        run(path, warm, 0)
+    medians = {True: [], False: []}
+    for r in range(repeats):
+        for path in paths:
+            medians[path].append(statistics.median(run(path, calls, r * calls)) * 1e6)
+    return medians
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=1000)
@@ -51,26 +102,9 @@ def main():
     if args.model == "decide":
         return main_decide(args)
     import torch
-    from howl_amd.context import InferenceContext
-    from howl_amd.data.transform.operator import ZmuvTransform
-    from howl_amd.data.transform.transform import StandardAudioTransform
-    from howl_amd.model import RegisteredModel
     from howl_amd.model.inference import FrameInferenceEngine
     from howl_amd.utils import audio_utils
-    from howl_amd.utils.synth import res8_closed_form_state, synthetic_pcm
-    dev = torch.device("cuda:0")
-    ctx = InferenceContext(["hey", "fire", "fox"], token_type="word", use_blank=False)
-    if args.model in ("las", "gru"):
-        torch.manual_seed(2024)
-        model = RegisteredModel.find_registered_class(args.model)(ctx.num_labels).to(dev)
-    else:
-        model = RegisteredModel.find_registered_class("res8")(ctx.num_labels).to(dev)
-        model.load_state_dict(res8_closed_form_state(ctx.num_labels), strict=False)
-    model.eval()
-    std = StandardAudioTransform().to(dev).eval()
-    zmuv = ZmuvTransform().to(dev)
-    clips = synthetic_pcm(8, 160000, seed=77).to(dev)                  # 8 clips of 10 s
-    zmuv.update(std(clips[:1, :16000]))
+    ctx, model, std, zmuv, clips = setup(args.model, use_blank=False)
     engine = FrameInferenceEngine(500, 63, model, zmuv, ctx)
     starts, chunk = audio_utils.stride_starts(160000, 500, 63, 16000)
     frames = [clip[s:s + chunk] for clip in clips for s in starts]     # views: 8 x 151 windows, walked round-robin
@@ -86,13 +120,7 @@ def main():
             times.append(time.perf_counter() - t0)
         return times
 
-    paths = [True] if args.fused_only else [False, True]
-    for fused in paths:
-        run(fused, args.warmup, 0)
-    medians = {True: [], False: []}
-    for r in range(args.repeats):
-        for fused in paths:
-            medians[fused].append(statistics.median(run(fused, args.windows, r * args.windows)) * 1e6)
+    medians = alternate([True] if args.fused_only else [False, True], run, args.warmup, args.windows, args.repeats)
 
     many = []
     session = model.stream_session(std, zmuv)
@@ -100,15 +128,7 @@ def main():
         stride = (160000 - chunk) // n // 2 * 2
         clip = clips[0, :chunk + (n - 1) * stride].contiguous()
         windows = clip.as_strided((n, chunk), (stride, 1))
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        fused_us = []
-        for i in range(60):
-            e0.record()
-            session.probabilities(windows)
-            e1.record()
-            e1.synchronize()
-            fused_us.append(e0.elapsed_time(e1) * 1e3)
-        row = {"windows_per_launch": n, "fused_launch_us_median": round(statistics.median(fused_us[10:]), 2)}
+        row = {"windows_per_launch": n, "fused_launch_us_median": round(launch_us(lambda: session.probabilities(windows)), 2)}
         if not args.fused_only and n > 1:
             eng = FrameInferenceEngine(500, 1000.0 * stride / 16000 + 1e-6, model, zmuv, ctx)
             assert audio_utils.stride_starts(clip.numel(), 500, eng.eval_stride_size_ms, 16000)[0] == [stride * k for k in range(n)]
@@ -150,14 +170,7 @@ def gru_per_step(model, std, zmuv, session, window):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     launch, queued = {}, {}
     for frames in (1, T):
-        us = []
-        for i in range(60):
-            e0.record()
-            session.probabilities(window, frames=frames)
-            e1.record()
-            e1.synchronize()
-            us.append(e0.elapsed_time(e1) * 1e3)
-        launch[min((frames + 4) // 2, t1)] = statistics.median(us[10:])
+        launch[min((frames + 4) // 2, t1)] = launch_us(lambda: session.probabilities(window, frames=frames))
         # 200 launches between one pair of events: per launch, the larger of the kernel's time and the host's time to issue it
         torch.cuda.synchronize()
         e0.record()
@@ -193,20 +206,9 @@ def gru_per_step(model, std, zmuv, session, window):
 def main_seq_lstm(args):
     import numpy as np
     import torch
-    from howl_amd.context import InferenceContext
-    from howl_amd.data.transform.operator import ZmuvTransform
-    from howl_amd.data.transform.transform import StandardAudioTransform
-    from howl_amd.model import RegisteredModel
     from howl_amd.model.inference import InferenceEngine
-    from howl_amd.utils.synth import synthetic_pcm
-    dev = torch.device("cuda:0")
-    ctx = InferenceContext(["hey", "fire", "fox"], token_type="word", use_blank=True)
-    torch.manual_seed(2024)
-    model = RegisteredModel.find_registered_class("seq-lstm")(ctx.num_labels).to(dev).eval().streaming()
-    std = StandardAudioTransform().to(dev).eval()
-    zmuv = ZmuvTransform().to(dev)
-    clips = synthetic_pcm(8, 160000, seed=77).to(dev)                  # 8 clips of 10 s
-    zmuv.update(std(clips[:1, :16000]))
+    ctx, model, std, zmuv, clips = setup("seq-lstm", use_blank=True)
+    model.streaming()
     engine = InferenceEngine(model, zmuv, ctx)
     engine.sequence = [0, 1, 2, 0, 1, 2, 0, 1, 2]                      # never present: every call walks all of its frames
     paths = [True] if args.fused_only else ([False] if args.eager_only else [False, True])
@@ -229,7 +231,7 @@ def main_seq_lstm(args):
     sizes = [int(v) for v in rng.integers(16000, 48001, 64)]
     many = [clips[i % 8, :n].contiguous() for i, n in enumerate(sizes)]
 
-    def run_many(fused, n):
+    def run_many(fused, n, first):
         engine.fused_chunks = fused
         times = []
         for i in range(n):
@@ -248,20 +250,10 @@ def main_seq_lstm(args):
            "calls_per_repeat": args.windows, "warmup_calls": args.warmup}
     for name, size in (("a_8000_sample_chunks", 8000), ("b_16000_sample_chunks", 16000)):
         chunks = chunks_of(size)
-        for fused in paths:
-            run_chunks(fused, chunks, args.warmup, 0)
-        med = {True: [], False: []}
-        for r in range(args.repeats):
-            for fused in paths:
-                med[fused].append(statistics.median(run_chunks(fused, chunks, args.windows, r * args.windows)) * 1e6)
+        med = alternate(paths, lambda fused, n, first: run_chunks(fused, chunks, n, first), args.warmup, args.windows, args.repeats)
         out[name] = {"fused_us_medians": [round(v, 2) for v in med[True]], "eager_us_medians": [round(v, 2) for v in med[False]]}
     n_many = max(2, args.windows // 20)
-    for fused in paths:
-        run_many(fused, max(1, args.warmup // 20))
-    med = {True: [], False: []}
-    for r in range(args.repeats):
-        for fused in paths:
-            med[fused].append(statistics.median(run_many(fused, n_many)) * 1e6)
+    med = alternate(paths, run_many, max(1, args.warmup // 20), n_many, args.repeats)
     out["c_infer_many_64_clips_1_to_3_s"] = {"calls_per_repeat": n_many, "frames_per_call": sum(1 + n // 200 for n in sizes),
                                             "fused_us_medians": [round(v, 2) for v in med[True]],
                                             "eager_loop_us_medians": [round(v, 2) for v in med[False]]}
@@ -271,18 +263,10 @@ def main_seq_lstm(args):
     # the kernel alone, between two HIP events
     session = model.stream_session(std, zmuv)
     pad = torch.nn.utils.rnn.pad_sequence(many, batch_first=True)
-    ns = torch.tensor(sizes, dtype=torch.int64, device=dev)
+    ns = torch.tensor(sizes, dtype=torch.int64, device=clips.device)
     kernel = {}
     for name, pcm, n_samples in (("a_N1_8000", clips[:1, :8000], None), ("b_N1_16000", clips[:1, :16000], None), ("c_N64_1_to_3_s", pad, ns)):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        us = []
-        for i in range(60):
-            e0.record()
-            session.probabilities(pcm, n_samples=n_samples, return_state=False)
-            e1.record()
-            e1.synchronize()
-            us.append(e0.elapsed_time(e1) * 1e3)
-        kernel[name] = round(statistics.median(us[10:]), 2)
+        kernel[name] = round(launch_us(lambda: session.probabilities(pcm, n_samples=n_samples, return_state=False)), 2)
     out["launch_us_median_between_hip_events"] = kernel
     torch.cuda.synchronize()
     print(json.dumps(out), flush=True)
@@ -291,56 +275,37 @@ def main_seq_lstm(args):
 def main_decide(args):
     import numpy as np
     import torch
-    from howl_amd.context import InferenceContext
-    from howl_amd.data.transform.operator import ZmuvTransform
-    from howl_amd.data.transform.transform import StandardAudioTransform
-    from howl_amd.model import RegisteredModel
     from howl_amd.model.decision import DeviceDecider
     from howl_amd.model.inference import FrameInferenceEngine, InferenceEngine
-    from howl_amd.utils.synth import res8_closed_form_state, synthetic_pcm
-    dev = torch.device("cuda:0")
-    std = StandardAudioTransform().to(dev).eval()
-    zmuv = ZmuvTransform().to(dev)
-    clips = synthetic_pcm(8, 160000, seed=77).to(dev)
-    zmuv.update(std(clips[:1, :16000]))
+    ctx, lstm, std, zmuv, clips = setup("seq-lstm", use_blank=True)
+    fctx, res8, _, _, _ = setup("res8", use_blank=False)      # (both engines behind the one ZMUV)
+    dev = clips.device
     rng = np.random.default_rng(7)
     sizes = [int(v) for v in rng.integers(16000, 48001, 64)]           # case (c)'s clips
     many = [clips[i % 8, :n].contiguous() for i, n in enumerate(sizes)]
 
-    ctx = InferenceContext(["hey", "fire", "fox"], token_type="word", use_blank=True)
-    torch.manual_seed(2024)
-    lstm = RegisteredModel.find_registered_class("seq-lstm")(ctx.num_labels).to(dev).eval().streaming()
-    seq = InferenceEngine(lstm, zmuv, ctx)
+    seq = InferenceEngine(lstm.streaming(), zmuv, ctx)
     seq.fused_chunks = True
     seq.sequence = [0, 1, 2, 0, 1, 2, 0, 1, 2]                         # never present: every call walks all of its frames
-    fctx = InferenceContext(["hey", "fire", "fox"], token_type="word", use_blank=False)
-    res8 = RegisteredModel.find_registered_class("res8")(fctx.num_labels).to(dev)
-    res8.load_state_dict(res8_closed_form_state(fctx.num_labels), strict=False)
-    res8.eval()
     frame = FrameInferenceEngine(500, 63, res8, zmuv, fctx)
     frame.sequence = [0, 1, 2, 0, 1, 2, 0, 1, 2]
 
-    def run(engine, on, n):
-        engine.device_decisions = on
-        times = []
-        for _ in range(n):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            engine.infer_many(many)
-            times.append(time.perf_counter() - t0)
-        return times
-
     def both(engine, calls, warm):
+        def run(on, n, first):
+            engine.device_decisions = on
+            times = []
+            for _ in range(n):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                engine.infer_many(many)
+                times.append(time.perf_counter() - t0)
+            return times
+
         engine.device_decisions = False
         want = (engine.infer_many(many), [list(h) for h in engine.clip_histories])
         engine.device_decisions = True
         assert (engine.infer_many(many), engine.clip_histories) == want, "the device decisions differ from the host replay"
-        for on in (False, True):
-            run(engine, on, warm)
-        med = {True: [], False: []}
-        for _ in range(args.repeats):
-            for on in (False, True):
-                med[on].append(statistics.median(run(engine, on, calls)) * 1e6)
+        med = alternate([False, True], run, warm, calls, args.repeats)
         return {"calls_per_repeat": calls, "history_entries_per_call": sum(len(h) for h in want[1]),
                 "host_decisions_us_medians": [round(v, 2) for v in med[False]], "device_decisions_us_medians": [round(v, 2) for v in med[True]]}
 
@@ -359,15 +324,7 @@ def main_decide(args):
         cfg, keep = decider._config(dev)
         nf = torch.tensor(n_frames, dtype=torch.int32, device=dev)
         dl = torch.tensor(deltas, dtype=torch.float64, device=dev)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        us = []
-        for _ in range(60):
-            e0.record()
-            ops.decide_clips(cfg, probs, nf, dl, max(n_frames))
-            e1.record()
-            e1.synchronize()
-            us.append(e0.elapsed_time(e1) * 1e3)
-        return round(statistics.median(us[10:]), 2)
+        return round(launch_us(lambda: ops.decide_clips(cfg, probs, nf, dl, max(n_frames))), 2)
 
     session = lstm.stream_session(std, zmuv)
     pad = torch.nn.utils.rnn.pad_sequence(many, batch_first=True)
