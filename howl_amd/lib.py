@@ -311,6 +311,18 @@ CNN_SIGNATURES = {
 CNN_SIZE_FUNCS = {"howl_cnn_supported": [c_int, c_int, c_int, c_int, c_int], "howl_cnn_workspace_bytes": [c_int, c_int, c_int, c_int],
                   "howl_cnn_out_rows": [c_int, c_int]}
 
+# The streaming small-cnn / seq-cnn entry points of ``include/howl_hip_cnn_stream.h`` (tables of their own:
+# ``tests/test_emu_cnn_stream.py`` checks them against that header)
+CNN_STREAM_TILE_ROWS = 8                                                            # HOWL_CNN_STREAM_TILE_ROWS
+CNN_STREAM_SIGNATURES = {
+    "howl_cnn_stream_windows": [POINTER(HowlCnnParams), POINTER(HowlCnnBuffers), P, c_long, c_int, c_int, P, c_int, c_float, P, c_int, P, P,
+                                P, c_size_t, STREAM],
+    "howl_cnn_stream_clips": [POINTER(HowlCnnParams), POINTER(HowlCnnBuffers), P, c_long, c_int, c_int, P, P, c_int, c_float, P, c_int, P, P,
+                              c_long, P, c_size_t, STREAM],
+}
+CNN_STREAM_SIZE_FUNCS = {"howl_cnn_stream_supported": [c_int, c_int, c_int, c_int], "howl_cnn_stream_workspace_bytes": [c_int, c_int, c_int],
+                         "howl_cnn_stream_rows": [c_int, c_int]}
+
 # The time-stretch entry point of ``include/howl_hip_timestretch.h`` (``tests/test_emu_timestretch.py`` checks the table against that
 # header).  ``clips_host`` is a HOST pointer to ``HowlStretchClip`` records (``STRETCH_CLIP_DTYPE``), ``clips_dev`` their device copy.
 TIMESTRETCH_SIGNATURES = {
@@ -361,13 +373,15 @@ class Library:
         self.cdll.howl_last_error.argtypes = []
         for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES, **LSTM_STREAM_SIGNATURES, **DECIDE_SIGNATURES,
                                **CTC_LONG_SIGNATURES, **GRU_SIGNATURES, **LAS_SIGNATURES, **LAS_STREAM_SIGNATURES,
-                               **GRU_STREAM_SIGNATURES, **TIMESTRETCH_SIGNATURES, **CNN_SIGNATURES, **DENSE_SIGNATURES}.items():
+                               **GRU_STREAM_SIGNATURES, **TIMESTRETCH_SIGNATURES, **CNN_SIGNATURES, **CNN_STREAM_SIGNATURES,
+                               **DENSE_SIGNATURES}.items():
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = c_int
             fn.argtypes = argtypes
         for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS, **LSTM_STREAM_SIZE_FUNCS, **DECIDE_SIZE_FUNCS,
                                **CTC_LONG_SIZE_FUNCS, **GRU_SIZE_FUNCS, **LAS_SIZE_FUNCS, **LAS_STREAM_SIZE_FUNCS,
-                               **GRU_STREAM_SIZE_FUNCS, **TIMESTRETCH_SIZE_FUNCS, **CNN_SIZE_FUNCS, **DENSE_SIZE_FUNCS}.items():
+                               **GRU_STREAM_SIZE_FUNCS, **TIMESTRETCH_SIZE_FUNCS, **CNN_SIZE_FUNCS, **CNN_STREAM_SIZE_FUNCS,
+                               **DENSE_SIZE_FUNCS}.items():
             fn = getattr(self.cdll, name)
             fn.restype = c_size_t
             fn.argtypes = argtypes

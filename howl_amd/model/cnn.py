@@ -18,9 +18,10 @@ from howl_amd import ops, parallel
 from howl_amd.settings import _EnvSettings
 
 from .base import RegisteredModel
-from .stream import PreparedStreamSession
+from .stream import PreparedStreamSession, StreamSession
 
-__all__ = ["Res8", "Res8Settings", "Res8StreamSession", "MobileNetClassifier", "CnnSettings", "SmallCnn", "SequentialCnn"]
+__all__ = ["Res8", "Res8Settings", "Res8StreamSession", "MobileNetClassifier", "CnnSettings", "SmallCnn", "SequentialCnn",
+           "SmallCnnStreamSession", "SeqCnnStreamSession"]
 
 
 class Res8Settings(_EnvSettings):
@@ -650,6 +651,60 @@ class _CnnFunction(torch.autograd.Function):
         return (None, None) + tuple(grads)
 
 
+class _CnnStreamSession(StreamSession):
+    """What the two sessions below share: the kernel reads the model's parameters and running statistics in place (no prepared
+    state, nothing to refresh), and the range query takes the model's kind in front."""
+    RUNS = "eval-mode BatchNorm (running statistics) and no dropout"
+
+    def in_range(self, n_samples, n_mels, n_labels):
+        return ops.cnn_stream_supported(self.model.KIND, n_samples, n_mels, n_labels)
+
+    def _launch_args(self, pcm):
+        N, L = pcm.shape
+        ws = self._workspace(ops.cnn_stream_workspace_bytes(self.model.KIND, N, L), pcm.device)
+        prm, buf = self.model._stream_records()
+        return prm, buf, pcm, self.std._standard_fb(), self.std.n_mels, self._pair(), self.model.num_labels, ws
+
+
+class SmallCnnStreamSession(_CnnStreamSession):
+    """Streaming small-cnn: ``probabilities(pcm)`` takes (N, L) raw PCM windows to their (N, C) class probabilities in ONE kernel
+    launch (``howl_cnn_stream_windows``: log-mel and ZMUV, both convolutions with their pools and BatchNorms, the head and the
+    softmax, one workgroup per window).  The kernel reads the model in place: a ``load_state_dict``, an optimiser step or a write
+    torch does not see is in the next call's answer.  The session owns its scratch, so two engines on two streams share nothing.
+    Eval mode only, standard filterbank only.  The kernel's range, which ``supported()`` answers for: 40 mel bins, 5000 .. 8199
+    samples (26 .. 41 frames), <= 64 labels."""
+
+    @torch.no_grad()
+    def probabilities(self, pcm: torch.Tensor, logits: torch.Tensor = None) -> torch.Tensor:
+        """pcm: (N, L) fp32 on the device, unit sample stride (rows may be overlapping views of one clip) -> (N, C) on the device."""
+        self._enter(pcm)
+        return ops.cnn_stream_windows(*self._launch_args(pcm), logits=logits)
+
+
+class SeqCnnStreamSession(_CnnStreamSession):
+    """Streaming seq-cnn: ``probabilities(pcm, n_samples)`` takes N ragged raw PCM clips to the class probabilities of their output
+    rows in ONE kernel launch (``howl_cnn_stream_clips``: one workgroup per clip and tile of ``lib.CNN_STREAM_TILE_ROWS`` output
+    rows).  The call shape is ``LstmStreamSession``'s, so the engine has one branch for both; the model carries no state.  Read in
+    place, eval mode only, standard filterbank only.  The kernel's range, which ``supported()`` answers for clips of UP TO
+    ``n_samples`` samples: 40 mel bins, 800 .. 1638399 samples (5 .. 8192 frames), <= 64 labels."""
+    UNIT = "chunks"
+
+    def rows_of(self, n_samples: int) -> int:
+        """Output rows (the engine's frames) of a clip of ``n_samples`` samples: ``SequentialCnn.compute_length(1 + n // 200)``."""
+        return ops.cnn_stream_rows(self.model.KIND, n_samples)
+
+    @torch.no_grad()
+    def probabilities(self, pcm: torch.Tensor, n_samples: torch.Tensor = None, state=None, return_state: bool = False,
+                      logits: torch.Tensor = None):
+        """pcm: (N, L_max) fp32 on the device, unit sample stride; ``n_samples`` (N) int64 on the device, the samples of each clip
+        (None: L_max for all) -> (probs (N, rows_of(L_max), C), None): rows behind a clip's last one are zero.  ``state`` must be
+        None and nothing is returned for it: the model carries none."""
+        if state is not None:
+            raise ValueError(f"{type(self).__name__}: seq-cnn carries no state between chunks")
+        self._enter(pcm)
+        return ops.cnn_stream_clips(*self._launch_args(pcm), n_samples=n_samples, logits=logits), None
+
+
 class _CnnBase(RegisteredModel):
     """The two-stage conv encoder both models share (``howl_amd/csrc/cnn.hip``): the whole model is one C-ABI call per direction,
     the ``nn`` submodules are parameter containers in the reference's construction order and with its ``state_dict`` keys
@@ -699,6 +754,19 @@ class _CnnBase(RegisteredModel):
     def out_rows(cls, T: int) -> int:
         """Rows of the encoder's output for T frames (0 outside the kernels' range): ``howl_cnn_out_rows``."""
         return int(_lib.get().cdll.howl_cnn_out_rows(cls.KIND, int(T)))
+
+    def _stream_records(self):
+        """``HowlCnnParams`` and ``HowlCnnBuffers`` over the tensors as they are now (the streaming launches read them in place)."""
+        b1, b2 = self.encoder1[3], self.encoder2[3]
+        prm = _lib.HowlCnnParams(*[_vp(p) for p in self.hot_parameters()])
+        buf = _lib.HowlCnnBuffers(_vp(b1.running_mean), _vp(b1.running_var), _vp(b1.num_batches_tracked), _vp(b2.running_mean),
+                                  _vp(b2.running_var), _vp(b2.num_batches_tracked))
+        return prm, buf
+
+    def stream_session(self, std, zmuv):
+        """One-launch inference from raw PCM for this model: ``SmallCnnStreamSession`` / ``SeqCnnStreamSession`` over ``std`` (a
+        ``StandardAudioTransform``) and ``zmuv`` (a ``ZmuvTransform`` or None)."""
+        return self.STREAM_SESSION(self, std, zmuv)
 
     def _draw_mask(self, shape, device):
         if self.forced_keep_mask is not None:
@@ -782,6 +850,7 @@ class SmallCnn(_CnnBase, name="small-cnn"):
     CONV0 = ((8, 16), (4, 0), (2, 2))
     LO, HI = 26, 41
     RANGE_NOTE = " (the encoder must leave exactly two rows for the head's 384 inputs)"
+    STREAM_SESSION = SmallCnnStreamSession
 
     @staticmethod
     def _head_inputs(config):
@@ -812,6 +881,7 @@ class SequentialCnn(_CnnBase, name="seq-cnn"):
     CONV0 = ((20, 16), (10, 0), (1, 2))
     LO, HI = 5, 8192
     RANGE_NOTE = " (fewer than 5 frames leave no output row)"
+    STREAM_SESSION = SeqCnnStreamSession
     DEFERS_CTC_MEAN = False     # FusedTrainer.step_sequence: the CTC launch writes the batch mean itself
 
     @staticmethod

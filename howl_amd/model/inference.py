@@ -20,7 +20,7 @@ from howl_amd.settings import SETTINGS
 from howl_amd.utils import audio_utils
 
 from .base import RegisteredModel
-from .cnn import Res8
+from .cnn import Res8, SequentialCnn, SmallCnn
 from .decision import DeviceDecider, ProbabilitySmoother, SequenceMatcher
 from .rnn import LASClassifier, SequentialLstm, SimpleGru, SimpleLstm
 
@@ -61,7 +61,8 @@ class InferenceEngine:
         self._matcher = SequenceMatcher(self.sequence, self.inference_window_ms, self.tolerance_window_ms)
         self.curr_time = 0
         self.label_history = []
-        # infer as ONE launch (LstmStreamSession) instead of the frontend + LSTM + head + softmax chain: off unless asked for
+        # infer as ONE launch (LstmStreamSession, SeqCnnStreamSession) instead of the frontend + model + softmax chain: off unless
+        # asked for
         self.fused_chunks = os.environ.get("HOWL_STREAM_FUSED") == "1"
         self._stream_session = None      # (see _session)
         # infer_many: the frame-by-frame decision logic of all clips as ONE launch behind the probabilities (DeviceDecider) instead
@@ -129,6 +130,9 @@ class InferenceEngine:
         """``LstmStreamSession`` for chunks of up to ``n_samples`` samples where the model is a ``kind`` (see ``_session``)."""
         return self._session(kind, n_samples)
 
+    # the sequential models with a chunk session (``probabilities(pcm, n_samples=, state=, return_state=)`` and ``rows_of``)
+    CHUNK_MODELS = (SequentialLstm, SequentialCnn)
+
     def _device_decider(self, mode: int, t_max: int, min_delta_ms: float, n_clips: int):
         """The decision launch for clips of up to ``t_max`` frames with the settings as they are now, or None when the switch is off
         or the configuration is outside the kernel's range: the caller then replays the logic on the host."""
@@ -159,7 +163,7 @@ class InferenceEngine:
         self.std = self.std.to(audio_data.device)
         session = None
         if self.fused_chunks and audio_data.dim() == 1 and audio_data.dtype == torch.float32:
-            session = self._lstm_session(SequentialLstm, audio_data.size(-1))
+            session = self._session(self.CHUNK_MODELS, audio_data.size(-1))
         if session is not None:      # one launch, one host copy; the carried state read and assigned as SequentialLstm.forward does
             streaming = self.model.is_streaming
             probs, state = session.probabilities(audio_data.reshape(1, -1), state=self.model.streaming_state if streaming else None,
@@ -185,7 +189,7 @@ class InferenceEngine:
         session = None
         if self.fused_chunks and clips and all(c.dim() == 1 and c.dtype == torch.float32 for c in clips):
             self.std = self.std.to(clips[0].device)
-            session = self._lstm_session(SequentialLstm, max(c.size(-1) for c in clips))
+            session = self._session(self.CHUNK_MODELS, max(c.size(-1) for c in clips))
             if session is not None and not session.supported(min(c.size(-1) for c in clips)):
                 session = None
         res = []
@@ -202,7 +206,7 @@ class InferenceEngine:
             pcm = torch.nn.utils.rnn.pad_sequence(group, batch_first=True)
             n_samples = torch.tensor(sizes, dtype=torch.int64).to(pcm.device)
             probs, _ = session.probabilities(pcm, n_samples=n_samples, return_state=False)
-            frames = [1 + n // 200 for n in sizes]
+            frames = [session.rows_of(n) for n in sizes]
             deltas = [int(n / self.sample_rate * 1000) / f for n, f in zip(sizes, frames)]      # as _run_frames divides
             decider = self._device_decider(0, max(frames), min(deltas), len(group))
             if decider is not None:
@@ -211,9 +215,9 @@ class InferenceEngine:
                 self.clip_histories.extend(histories)
                 continue
             probs = probs.cpu().numpy()
-            for n, row in zip(sizes, probs):
+            for n, f, row in zip(sizes, frames, probs):
                 self.reset()
-                res.append(self._run_frames(row[:1 + n // 200], int(n / self.sample_rate * 1000)))
+                res.append(self._run_frames(row[:f], int(n / self.sample_rate * 1000)))
                 self.clip_histories.append(list(self.label_history))
         self.reset()
         return res
@@ -223,8 +227,8 @@ class FrameInferenceEngine(InferenceEngine):
     def __init__(self, max_window_size_ms: int, eval_stride_size_ms: int, *args):
         super().__init__(*args)
         self.max_window_size_ms, self.eval_stride_size_ms = max_window_size_ms, eval_stride_size_ms
-        # ingest_frame as ONE launch (Res8StreamSession, LasStreamSession, GruStreamSession) instead of the frontend + model +
-        # softmax chain: off unless asked for
+        # ingest_frame as ONE launch (Res8StreamSession, LasStreamSession, GruStreamSession, SmallCnnStreamSession) instead of the
+        # frontend + model + softmax chain: off unless asked for
         self.fused_windows = os.environ.get("HOWL_STREAM_FUSED") == "1"
         self._frames_cache = {}
 
@@ -394,7 +398,7 @@ class FrameInferenceEngine(InferenceEngine):
             return None
         if isinstance(self.model, SimpleLstm) and self._window_frames(frame) is None:
             return None      # (a window with no whole 512-sample frame has compute_lengths < 1: the chain's business)
-        return self._session((Res8, LASClassifier, SimpleGru, SimpleLstm), frame.size(-1))
+        return self._session((Res8, LASClassifier, SimpleGru, SimpleLstm, SmallCnn), frame.size(-1))
 
     @torch.no_grad()
     def ingest_frame(self, frame: torch.Tensor, curr_time: float = None) -> int:

@@ -288,6 +288,11 @@ class LstmStreamSession(StreamSession):
         self.last_only = isinstance(model, SimpleLstm)
         self._own = None      # the state pair this session returned last: handed back, it is advanced in place
 
+    @staticmethod
+    def rows_of(n_samples: int) -> int:
+        """Rows of ``probs`` (the engine's frames) a chunk of ``n_samples`` samples has: one per frame."""
+        return 1 + n_samples // 200
+
     @torch.no_grad()
     def probabilities(self, pcm: torch.Tensor, n_samples: torch.Tensor = None, frames: torch.Tensor = None, state=None,
                       return_state: bool = True, logits: torch.Tensor = None):

@@ -420,6 +420,55 @@ def gru_stream_windows(prm, buffers, pcm, frames: int, fbp, n_mels, zmuv_pair, n
     return probs
 
 
+# ---- streaming small-cnn / seq-cnn (include/howl_hip_cnn_stream.h): one launch from the PCM to the probabilities --------------------
+# (the queries take the kind first: ``_lib.CNN_SMALL`` or ``_lib.CNN_SEQ``)
+
+cnn_stream_supported = _stream_query("howl_cnn_stream_supported", bool)
+cnn_stream_workspace_bytes = _stream_query("howl_cnn_stream_workspace_bytes", int)
+cnn_stream_rows = _stream_query("howl_cnn_stream_rows", int)
+
+
+def cnn_stream_windows(prm, buffers, pcm, fbp, n_mels, zmuv_pair, n_labels, ws, probs=None, logits=None, log_eps: float = 1e-7):
+    """small-cnn: (N, L) PCM windows (unit sample stride, any row stride: overlapping views of one clip are fine) -> (N, C)
+    probabilities in one launch; ``prm`` / ``buffers``: ``HowlCnnParams`` / ``HowlCnnBuffers`` records, read in place; ``ws``: uint8
+    scratch of ``cnn_stream_workspace_bytes(CNN_SMALL, N, L)``; ``logits`` (N, C), when given, receives the pre-softmax scores."""
+    if pcm.dim() != 2:
+        raise ValueError("pcm must be (N, L)")
+    if pcm.stride(1) != 1:
+        pcm = pcm.contiguous()
+    if not on_device(pcm) or pcm.dtype != torch.float32:
+        _p(pcm)
+    N, L = pcm.shape
+    if probs is None:
+        probs = torch.empty((N, n_labels), dtype=torch.float32, device=pcm.device)
+    _lib.get().call("howl_cnn_stream_windows", ctypes.byref(prm), ctypes.byref(buffers), ctypes.c_void_p(pcm.data_ptr()), pcm.stride(0), N,
+                    L, _p(fbp), int(n_mels), log_eps, _p(zmuv_pair, allow_none=True), int(n_labels), _p(probs),
+                    _p(logits, allow_none=True), _p(ws, torch.uint8), ws.numel(), _stream())
+    return probs
+
+
+def cnn_stream_clips(prm, buffers, pcm, fbp, n_mels, zmuv_pair, n_labels, ws, n_samples=None, probs=None, logits=None,
+                     log_eps: float = 1e-7):
+    """seq-cnn: (N, L_max) PCM clips (unit sample stride, any row stride) -> (N, cnn_stream_rows(CNN_SEQ, L_max), C) probabilities
+    in one launch, the rows behind a clip's own written as zeros.  ``n_samples``: (N) int64 on the device or None (L_max for every
+    clip); ``ws``: uint8 scratch of ``cnn_stream_workspace_bytes(CNN_SEQ, N, L_max)``; ``logits``, when given, receives the
+    pre-softmax scores in the layout of ``probs``."""
+    if pcm.dim() != 2:
+        raise ValueError("pcm must be (N, L_max)")
+    if pcm.stride(1) != 1:
+        pcm = pcm.contiguous()
+    if not on_device(pcm) or pcm.dtype != torch.float32:
+        _p(pcm)
+    N, L = pcm.shape
+    if probs is None:
+        probs = torch.empty((N, cnn_stream_rows(_lib.CNN_SEQ, L), n_labels), dtype=torch.float32, device=pcm.device)
+    _lib.get().call("howl_cnn_stream_clips", ctypes.byref(prm), ctypes.byref(buffers), ctypes.c_void_p(pcm.data_ptr()),
+                    pcm.stride(0) if N > 1 else L, N, L, _p(n_samples, torch.int64, allow_none=True), _p(fbp), int(n_mels), log_eps,
+                    _p(zmuv_pair, allow_none=True), int(n_labels), _p(probs), _p(logits, allow_none=True), probs.stride(0),
+                    _p(ws, torch.uint8), ws.numel(), _stream())
+    return probs
+
+
 # ---- streaming seq-lstm / lstm (include/howl_hip_lstm_stream.h): one launch from N PCM chunks to their frame probabilities --------
 
 lstm_stream_supported = _stream_query("howl_lstm_stream_supported", bool)

@@ -22,7 +22,13 @@ kernel alone between two HIP events for each of the three shapes.
 (``device_decisions`` off / on, DeviceDecider), alternating repeat by repeat, in one process: (d) ``InferenceEngine`` (seq-lstm,
 ``HOWL_STREAM_FUSED=1``) with the settings of (c), (e) the same with the blank weighted down so that most frames reach the smoother
 and the matcher, (f) ``FrameInferenceEngine`` (res8) on the same clips; and ``howl_decide_clips`` alone between two HIP events on
-the probabilities of each.  Each pair is checked for equal results first."""
+the probabilities of each.  Each pair is checked for equal results first.
+
+``--model small-cnn``: the protocol of ``--model las`` for the small-cnn model (SmallCnnStreamSession).
+
+``--model seq-cnn``: the protocol of ``--model seq-lstm`` for the seq-cnn model (SeqCnnStreamSession; the model carries no state), and
+in addition case (c) with the decision logic on the device (``device_decisions`` on: fused + DeviceDecider against fused alone,
+alternating).  The eager leg of every pair is the launch chain the engines run with the switch off."""
 import argparse
 import json
 import os
@@ -50,7 +56,11 @@ def setup(model_name, use_blank):
     ctx = InferenceContext(["hey", "fire", "fox"], token_type="word", use_blank=use_blank)
     if model_name != "res8":
         torch.manual_seed(2024)
-    model = RegisteredModel.find_registered_class(model_name)(ctx.num_labels).to(dev)
+    if model_name in ("small-cnn", "seq-cnn"):      # (the head's width is the settings', as in the reference)
+        from howl_amd.model import CnnSettings
+        model = RegisteredModel.find_registered_class(model_name)(ctx.num_labels, CnnSettings(num_labels=ctx.num_labels)).to(dev)
+    else:
+        model = RegisteredModel.find_registered_class(model_name)(ctx.num_labels).to(dev)
     if model_name == "res8":
         model.load_state_dict(res8_closed_form_state(ctx.num_labels), strict=False)
     model.eval()
@@ -95,10 +105,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--fused-only", action="store_true", help="skip the eager path (a kernel-trace pass over the one launch)")
     ap.add_argument("--eager-only", action="store_true", help="seq-lstm: skip the fused path (a kernel-trace pass over the launch chain)")
-    ap.add_argument("--model", choices=["res8", "las", "gru", "seq-lstm", "decide"], default="res8")
+    ap.add_argument("--model", choices=["res8", "las", "gru", "seq-lstm", "decide", "small-cnn", "seq-cnn"], default="res8")
     args = ap.parse_args()
-    if args.model == "seq-lstm":
-        return main_seq_lstm(args)
+    if args.model in ("seq-lstm", "seq-cnn"):
+        return main_seq_lstm(args, args.model)
     if args.model == "decide":
         return main_decide(args)
     import torch
@@ -124,7 +134,7 @@ def main():
 
     many = []
     session = model.stream_session(std, zmuv)
-    for n in ((1, 64, 256) if args.model in ("las", "gru") else (64, 256)):
+    for n in ((1, 64, 256) if args.model in ("las", "gru", "small-cnn") else (64, 256)):
         stride = (160000 - chunk) // n // 2 * 2
         clip = clips[0, :chunk + (n - 1) * stride].contiguous()
         windows = clip.as_strided((n, chunk), (stride, 1))
@@ -203,11 +213,11 @@ def gru_per_step(model, std, zmuv, session, window):
             "eager_launches_us": eager, "gru_fwd4_steps": t1, "gru_fwd4_us_per_step": round(eager["gru_fwd"] / t1, 3)}
 
 
-def main_seq_lstm(args):
+def main_seq_lstm(args, model_name="seq-lstm"):
     import numpy as np
     import torch
     from howl_amd.model.inference import InferenceEngine
-    ctx, model, std, zmuv, clips = setup("seq-lstm", use_blank=True)
+    ctx, model, std, zmuv, clips = setup(model_name, use_blank=True)
     model.streaming()
     engine = InferenceEngine(model, zmuv, ctx)
     engine.sequence = [0, 1, 2, 0, 1, 2, 0, 1, 2]                      # never present: every call walks all of its frames
@@ -246,7 +256,8 @@ def main_seq_lstm(args):
             times.append(time.perf_counter() - t0)
         return times
 
-    out = {"metric": "InferenceEngine.infer / infer_many wall time per call, us (seq-lstm, host copy included; median of each repeat)",
+    out = {"model": model_name,
+           "metric": f"InferenceEngine.infer / infer_many wall time per call, us ({model_name}, host copy included; median of each repeat)",
            "calls_per_repeat": args.windows, "warmup_calls": args.warmup}
     for name, size in (("a_8000_sample_chunks", 8000), ("b_16000_sample_chunks", 16000)):
         chunks = chunks_of(size)
@@ -254,14 +265,28 @@ def main_seq_lstm(args):
         out[name] = {"fused_us_medians": [round(v, 2) for v in med[True]], "eager_us_medians": [round(v, 2) for v in med[False]]}
     n_many = max(2, args.windows // 20)
     med = alternate(paths, run_many, max(1, args.warmup // 20), n_many, args.repeats)
-    out["c_infer_many_64_clips_1_to_3_s"] = {"calls_per_repeat": n_many, "frames_per_call": sum(1 + n // 200 for n in sizes),
+    session = model.stream_session(std, zmuv)
+    out["c_infer_many_64_clips_1_to_3_s"] = {"calls_per_repeat": n_many, "frames_per_call": sum(session.rows_of(n) for n in sizes),
                                             "fused_us_medians": [round(v, 2) for v in med[True]],
                                             "eager_loop_us_medians": [round(v, 2) for v in med[False]]}
+    if model_name == "seq-cnn" and not args.eager_only:
+        # (c) again, both legs fused: the decision logic on the host (False) against DeviceDecider (True)
+        def run_decide(on, n, first):
+            engine.device_decisions = on
+            return run_many(True, n, first)
+        engine.fused_chunks, engine.device_decisions = True, False
+        want = (engine.infer_many(many), [list(h) for h in engine.clip_histories])
+        engine.device_decisions = True
+        assert (engine.infer_many(many), engine.clip_histories) == want, "the device decisions differ from the host replay"
+        med = alternate([False, True], run_decide, max(1, args.warmup // 20), n_many, args.repeats)
+        engine.device_decisions = False
+        out["d_infer_many_64_clips_fused_decisions_host_vs_device"] = {
+            "calls_per_repeat": n_many, "fused_host_decisions_us_medians": [round(v, 2) for v in med[False]],
+            "fused_device_decisions_us_medians": [round(v, 2) for v in med[True]]}
     if args.eager_only:
         print(json.dumps(out), flush=True)
         return
     # the kernel alone, between two HIP events
-    session = model.stream_session(std, zmuv)
     pad = torch.nn.utils.rnn.pad_sequence(many, batch_first=True)
     ns = torch.tensor(sizes, dtype=torch.int64, device=clips.device)
     kernel = {}
