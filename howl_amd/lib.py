@@ -335,6 +335,25 @@ TIMESTRETCH_MIN_SAMPLES = 2048                                                  
 STRETCH_CLIP_FIELDS = [("rate", "<f8"), ("src_row", "<i8"), ("dst_off", "<i8"), ("len", "<i4"), ("out_len", "<i4"), ("n_out", "<i4"),
                        ("bg_idx", "<i4"), ("bg_off", "<i4"), ("alpha", "<f4")]
 
+# The resampler of ``include/howl_hip_resample.h`` (``tests/test_emu_resample.py`` checks the tables against that header).  ``plan``,
+# ``clips_host`` and the bank written by ``howl_resample_bank`` are HOST pointers; ``clips_dev`` is the records' device copy.
+class HowlResamplePlan(ctypes.Structure):
+    _fields_ = [("sr_in", c_int), ("sr_out", c_int), ("up", c_int), ("down", c_int), ("taps", c_int), ("j_lo", c_int), ("j_hi", c_int),
+                ("reserved", c_int), ("s", c_double)]
+
+
+RESAMPLE_SIGNATURES = {
+    "howl_resample_plan": [c_int, c_int, POINTER(HowlResamplePlan)],
+    "howl_resample_bank": [POINTER(HowlResamplePlan), c_void_p],
+    "howl_resample_clips": [P, c_long, c_int, c_int, P, c_long, POINTER(HowlResamplePlan), c_void_p, P, c_int, P, c_long, STREAM],
+}
+RESAMPLE_SIZE_FUNCS = {"howl_resample_bank_floats": [POINTER(HowlResamplePlan)], "howl_resample_out_len": [POINTER(HowlResamplePlan), c_long]}
+RESAMPLE_F32, RESAMPLE_I16 = 0, 1                                                   # HOWL_RESAMPLE_F32 / _I16
+RESAMPLE_MAX_CLIPS = 8192                                                           # HOWL_RESAMPLE_MAX_CLIPS
+RESAMPLE_MAX_FRAMES = 1 << 24                                                       # HOWL_RESAMPLE_MAX_FRAMES
+# ``HowlResampleClip`` as a numpy record (24 bytes, no padding)
+RESAMPLE_CLIP_FIELDS = [("src_off", "<i8"), ("dst_off", "<i8"), ("len", "<i4"), ("out_len", "<i4")]
+
 # The tests' door to the dense kernels of ``howl_gemm.hip.h``: ``include/howl_hip_dense.h`` (``tests/test_emu_dense.py`` checks the
 # tables against that header)
 DENSE_LIN = 1 << 30                                                                 # HOWL_DENSE_LIN
@@ -373,14 +392,14 @@ class Library:
         self.cdll.howl_last_error.argtypes = []
         for name, argtypes in {**SIGNATURES, **STREAM_SIGNATURES, **LSTM_STREAM_SIGNATURES, **DECIDE_SIGNATURES,
                                **CTC_LONG_SIGNATURES, **GRU_SIGNATURES, **LAS_SIGNATURES, **LAS_STREAM_SIGNATURES,
-                               **GRU_STREAM_SIGNATURES, **TIMESTRETCH_SIGNATURES, **CNN_SIGNATURES, **CNN_STREAM_SIGNATURES,
+                               **GRU_STREAM_SIGNATURES, **TIMESTRETCH_SIGNATURES, **RESAMPLE_SIGNATURES, **CNN_SIGNATURES, **CNN_STREAM_SIGNATURES,
                                **DENSE_SIGNATURES}.items():
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = c_int
             fn.argtypes = argtypes
         for name, argtypes in {**SIZE_FUNCS, **STREAM_SIZE_FUNCS, **LSTM_STREAM_SIZE_FUNCS, **DECIDE_SIZE_FUNCS,
                                **CTC_LONG_SIZE_FUNCS, **GRU_SIZE_FUNCS, **LAS_SIZE_FUNCS, **LAS_STREAM_SIZE_FUNCS,
-                               **GRU_STREAM_SIZE_FUNCS, **TIMESTRETCH_SIZE_FUNCS, **CNN_SIZE_FUNCS, **CNN_STREAM_SIZE_FUNCS,
+                               **GRU_STREAM_SIZE_FUNCS, **TIMESTRETCH_SIZE_FUNCS, **RESAMPLE_SIZE_FUNCS, **CNN_SIZE_FUNCS, **CNN_STREAM_SIZE_FUNCS,
                                **DENSE_SIZE_FUNCS}.items():
             fn = getattr(self.cdll, name)
             fn.restype = c_size_t

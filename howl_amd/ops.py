@@ -177,6 +177,59 @@ def time_stretch(bank, records, records_dev, total, bg=None, through_transform=F
     return out[:total]
 
 
+_RESAMPLE_PLANS = {}
+
+
+def resample_plan(sr_in: int, sr_out: int):
+    """``howl_resample_plan`` for a rate pair -> (``HowlResamplePlan``, the host bank as a (up, taps) float32 array), computed
+    once per pair.  A pair outside the supported range raises ``HowlHipError`` with the pair in its message."""
+    key = (int(sr_in), int(sr_out))
+    if key not in _RESAMPLE_PLANS:
+        plan = _lib.HowlResamplePlan()
+        lib = _lib.get()
+        lib.call("howl_resample_plan", key[0], key[1], ctypes.byref(plan))
+        bank = np.empty((plan.up, plan.taps), dtype=np.float32)
+        assert lib.cdll.howl_resample_bank_floats(ctypes.byref(plan)) == bank.size
+        lib.call("howl_resample_bank", ctypes.byref(plan), ctypes.c_void_p(bank.ctypes.data))
+        _RESAMPLE_PLANS[key] = (plan, bank)
+    return _RESAMPLE_PLANS[key]
+
+
+def resample_out_len(plan, length: int) -> int:
+    """ceil(length * up / down): the full output length of a clip of ``length`` frames."""
+    return (int(length) * plan.up + plan.down - 1) // plan.down
+
+
+def resample_records(src_offs, lengths, dst_offs, out_lens):
+    """``HowlResampleClip`` records (``lib.RESAMPLE_CLIP_FIELDS``): clip b is frames ``src_offs[b] .. + lengths[b]`` of the source
+    and becomes ``out[dst_offs[b] .. + out_lens[b])``."""
+    rec = np.zeros(len(lengths), dtype=np.dtype(_lib.RESAMPLE_CLIP_FIELDS))
+    rec["src_off"], rec["dst_off"], rec["len"], rec["out_len"] = src_offs, dst_offs, lengths, out_lens
+    return rec
+
+
+def resample_clips(src, channels: int, plan, bank_dev, records, records_dev, out):
+    """Channel mean + band-limited resampling of a batch of ragged clips in one launch (``howl_resample_clips``), written into
+    ``out`` (a flat float32 device buffer: a dense (N, max_len) bank viewed flat, or a ragged flat bank) at the records'
+    ``dst_off``; nothing else of ``out`` is touched.  ``src``: the raw interleaved samples on the device, int16 or float32, flat;
+    ``bank_dev``: ``resample_plan``'s bank on the device; ``records`` (``resample_records``) are read on the host,
+    ``records_dev`` (the same bytes in device memory, e.g. an int64 tensor) by the kernel."""
+    records = np.ascontiguousarray(records)
+    if records.dtype.itemsize != 24:
+        raise TypeError("records must be HowlResampleClip records (ops.resample_records)")
+    fmt = {torch.float32: _lib.RESAMPLE_F32, torch.int16: _lib.RESAMPLE_I16}.get(src.dtype)
+    if fmt is None:
+        raise TypeError(f"expected float32 or int16 samples, got {src.dtype}")
+    if not on_device(records_dev):
+        _p(records_dev)
+    if records_dev.numel() * records_dev.element_size() < records.nbytes or records_dev.data_ptr() % 8:
+        raise ValueError("records_dev must hold the records' bytes at an 8-byte aligned address")
+    _lib.get().call("howl_resample_clips", _p(src, src.dtype), src.numel(), fmt, int(channels), _p(bank_dev), bank_dev.numel(),
+                    ctypes.byref(plan), ctypes.c_void_p(records.ctypes.data), ctypes.c_void_p(records_dev.data_ptr()), len(records),
+                    _p(out), out.numel(), _stream())
+    return out
+
+
 def gather_windows(bank, idx, start, length, dst_off, lout):
     """Rows ``bank[idx[b], start[b]:start[b]+length[b]]`` placed at column ``dst_off[b]`` of a zero (B, lout) batch."""
     B = idx.numel()

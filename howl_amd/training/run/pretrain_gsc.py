@@ -25,7 +25,7 @@ from howl_amd.data.transform.transform import StandardAudioTransform
 from howl_amd.model import RegisteredModel
 from howl_amd.model.cnn import require_supported_labels, require_supported_mels
 from howl_amd.settings import SETTINGS
-from howl_amd.training.data import ClipBank, load_gsc_splits, read_wav16k, synthetic_bank
+from howl_amd.training.data import ClipBank, load_gsc_splits, synthetic_bank
 from howl_amd.training.fused import FusedTrainer
 from howl_amd.utils.random_utils import set_random_seed
 from howl_amd.workspace import Workspace
@@ -90,7 +90,9 @@ def main(argv=None):
         test = synthetic_bank(max(args.synthetic // 8, 16), max_len, num_labels, device, seed=3)
     else:
         splits = load_gsc_splits(Path(SETTINGS.dataset.dataset_path), SETTINGS.training.vocab)
-        train, dev, test = (ClipBank([read_wav16k(p) for p, _ in s], [l for _, l in s], max_len, device) for s in splits)
+        # files of any rate, channel count and PCM width: raw samples up, resampled on the device into the rows
+        train, dev, test = (ClipBank.from_files([p for p, _ in s], [l for _, l in s], max_len, device, sample_rate=sample_rate)
+                            for s in splits)
 
     std_transform = StandardAudioTransform().to(device).eval()
     zmuv_transform = ZmuvTransform().to(device)

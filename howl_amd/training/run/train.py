@@ -121,21 +121,28 @@ def main(argv=None):
     seq = list(SETTINGS.inference_engine.inference_sequence)
 
     # ---- datasets -> device clip banks ----------------------------------------------------------------------------
+    # files of any rate, channel count and PCM width: the banks upload the raw samples and resample on the device
+    # (WakeWordClipBank.from_files); next to --synthetic clips the files are decoded on the host as before (16 kHz mono int16)
     splits = {"training": ([], []), "dev": ([], []), "test": ([], [])}
     for ds_path in args.dataset_paths:
         for name, records in zip(("training", "dev", "test"), load_howl_splits(Path(ds_path))):
             for m in records:
-                splits[name][0].append(read_wav16k(m.path))
+                splits[name][0].append(read_wav16k(m.path) if args.synthetic else m.path)
                 splits[name][1].append(m)
+
+    def make_bank(clips, metadata):
+        if args.synthetic:
+            return WakeWordClipBank(clips, metadata, ctx.labeler, device)
+        return WakeWordClipBank.from_files(clips, metadata, ctx.labeler, device, sample_rate=SETTINGS.audio.sample_rate)
     if args.synthetic:
         for name, n_pos, n_neg in (("training", args.synthetic, args.synthetic // 2), ("dev", 32, 32)):
             for positive, n in ((True, n_pos), (False, n_neg)):
                 c, m = synthetic_split(n, positive, vocab, seq, rng)
                 splits[name][0].extend(c)
                 splits[name][1].extend(m)
-    train_bank = WakeWordClipBank(*splits["training"], ctx.labeler, device)
+    train_bank = make_bank(*splits["training"])
     if splits["dev"][0]:
-        dev_bank = WakeWordClipBank(*splits["dev"], ctx.labeler, device)
+        dev_bank = make_bank(*splits["dev"])
     else:
         logging.warning("no dev split in the datasets: the engine evaluation (results CSV, best-model score) runs on TRAINING clips")
         dev_bank = train_bank
